@@ -11,6 +11,13 @@ A timed step ends with the result readout: the per-source, per-depth counts of e
 (hgx_bfs_result_counts: one counting launch per level over the device rows + one D2H), as
 BASELINE.md section 2 times "to the last D2H of results".
 
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) is the headline alone: it builds the
+config-2 snapshot, warms up, times the N steps and prints the line.  `--full` adds every other leg
+(the CPU baselines, config 3, config 4, config 5, the order-exact sequence legs), each of which the
+--no-* options can drop again.  `--dump-outputs DIR` writes what the last timed step returned
+(dump_outputs below) so two builds can be compared output for output; the inputs are seeded and the
+same from run to run.
+
 Multi-GPU: `python bench.py --gpus N` launches N ranks itself (one process per GPU, RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* set for each) unless it already runs under
 torch.distributed.run, in which case WORLD_SIZE must equal N.  Config 2: the sources are
@@ -725,6 +732,40 @@ def dropin_config2(args, ctx, snap, g):
     return out
 
 
+DUMP_SEEDS = 8          # sources whose visited sets --dump-outputs writes
+DUMP_SET_CAP = 65536    # atoms kept of one visited set (a larger set is sampled)
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what the caller of the timed step holds after its last step, as float64 .npy files
+    (ids and counts are exact in float64), ~20 MB at most:
+      counts.npy          [sources, depth + 1] |V_d| of every source -- the step's readout, whole;
+      visited_index.npy   [k, 4] rows (source index, depth, |V_d|, atoms written) of the sampled sets;
+      visited_atoms.npy   the sampled sets' ascending atom ids, one after the other in visited_index order.
+    The device-resident visited sets are too large to write whole (config 2: ~1e10 ids), so the sample is
+    fixed: DUMP_SEEDS source indices drawn with a seeded generator, every depth of each, and of a set above
+    DUMP_SET_CAP atoms the DUMP_SET_CAP positions a seeded generator draws (the same positions whenever the
+    set has the same size)."""
+    os.makedirs(path, exist_ok=True)
+    counts = res.counts()
+    np.save(os.path.join(path, "counts.npy"), counts.astype(np.float64))
+    rng = np.random.default_rng(20240607)
+    picks = np.sort(rng.choice(res.n_seeds, size=min(DUMP_SEEDS, res.n_seeds), replace=False))
+    index, atoms = [], []
+    for i in picks:
+        for d in range(res.n_levels):
+            v = res.visited(int(i), d)
+            n = len(v)
+            if n > DUMP_SET_CAP:
+                pos = np.sort(np.random.default_rng(n).choice(n, size=DUMP_SET_CAP, replace=False))
+                v = v[pos]
+            index.append((int(i), d, n, len(v)))
+            atoms.append(v.astype(np.float64))
+    np.save(os.path.join(path, "visited_index.npy"), np.asarray(index, np.float64).reshape(-1, 4))
+    np.save(os.path.join(path, "visited_atoms.npy"), np.concatenate(atoms) if atoms else np.zeros(0, np.float64))
+    log(f"outputs of the last timed step written to {path}: counts {counts.shape}, {len(index)} visited sets sampled")
+
+
 _JSON_FD = None
 
 
@@ -830,10 +871,19 @@ def main():
     ap.add_argument("--c4-timeout", type=float, default=420.0,
                     help="seconds after which the config-4 legs are abandoned (the line is still printed)")
     ap.add_argument("--dry-run", action="store_true", help="launch the ranks and join the group only (no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: CPU baselines, config 3 (pattern queries), config 4, "
+                         "config 5 and the order-exact sequence (drop-in) legs; the --no-* options pick among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's results as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.dry_run:
         dry_run(args)
         return
+    if not args.full:   # a plain run is the headline alone: config 2, set-up, warm-up, the timed steps, the line
+        args.no_queries = args.no_cpu_baseline = args.no_config4 = args.no_config5 = args.no_dropin = True
 
     # a progress line every 30 s on stderr: the CPU-baseline legs run minutes inside one C call (16
     # complete config-2 traversals: ~70-110 s) and a silent run of 3 minutes is taken for a hung one
@@ -898,14 +948,16 @@ def main():
     t0 = time.perf_counter()
     readout = 0
     phase = {"bfs_batch": 0.0, "readout": 0.0, "stats+close": 0.0}   # host wall split of the steps
-    for _ in range(args.steps):
+    keep_last = args.dump_outputs is not None   # --dump-outputs reads the last step's result after the timer
+    for i in range(args.steps):
         ta = time.perf_counter()
         res = H.bfs_batch(snap, g["seeds"], args.depth)
         tb = time.perf_counter()
         readout += int(res.counts().sum())   # the result readout: per-source per-depth counts (D2H)
         tc = time.perf_counter()
         stats.append(res.stats(accounting=False, raw=True))
-        res.close()
+        if not (keep_last and i == args.steps - 1):
+            res.close()
         phase["bfs_batch"] += tb - ta
         phase["readout"] += tc - tb
         phase["stats+close"] += time.perf_counter() - tc
@@ -915,6 +967,10 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0)
     stats = [x.as_dict() for x in stats]
     assert readout == args.steps * acct_visits, "readout differs from the warm-up batch"
+    if keep_last:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, res)
+        res.close()
     edges_total = sum_over_ranks(acct["traversed_edges"] * args.steps)
     teps = edges_total / dt
     roof, per_kernel = roofline(stats, "config2")

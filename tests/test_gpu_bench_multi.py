@@ -12,7 +12,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "2", "--steps", "1", "--warmup", "1", "--scale", "0.005", "--sources", "64", "--no-queries",
+ARGS = ["--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--scale", "0.005", "--sources", "64", "--no-queries",
         "--no-config5", "--no-cpu-baseline", "--c4-scale", "0.005", "--c4-timeout", "100"]
 
 

@@ -7,7 +7,7 @@
 set -u
 TAG=${1:-r01}
 shift || true
-ARGS=${@:-"--steps 3 --warmup 1 --no-cpu-baseline"}
+ARGS=${@:-"--full --steps 3 --warmup 1 --no-cpu-baseline"}
 OUT=gpurun_out/prof_${TAG}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
