@@ -54,6 +54,8 @@ HGX_OPT_SEQ_TLIMIT = 18
 HGX_OPT_SEQ_PACK_MIN = 19
 HGX_OPT_XB_FLAT = 20
 HGX_OPT_XB_STATIC = 21
+HGX_OPT_SP_BUDGET = 22   # include/hgx_paths.h
+HGX_NO_GOAL = -1
 
 # Every symbol include/hgx.h declares (checked by tests/test_abi.py without a GPU).
 EXPORTED = (
@@ -71,6 +73,13 @@ EXPORTED = (
     "hgx_query_set_free", "hgx_pattern_batch_set_into", "hgx_query_set_info", "hgx_snapshot_read_handles",
     "hgx_snapshot_writer_begin", "hgx_snapshot_writer_handles", "hgx_snapshot_writer_end", "hgx_snapshot_writer_abort", "hgx_snapshot_writer_handle_bytes",
     "hgx_bfs_result_visited_range", "hgx_seq_result_pairs_range",
+)
+
+# Every symbol include/hgx_paths.h declares (checked by tests/test_sp_ref.py without a GPU).
+EXPORTED_PATHS = (
+    "hgx_link_weights_create", "hgx_link_weights_free", "hgx_shortest_paths", "hgx_sp_result_info",
+    "hgx_sp_result_distances", "hgx_sp_result_path", "hgx_sp_result_distance_row", "hgx_sp_result_predecessor_row",
+    "hgx_sp_result_stats", "hgx_sp_result_free",
 )
 
 
@@ -223,6 +232,18 @@ def lib():
         "hgx_pattern_batch_set": ([vp, vp, C.POINTER(vp)], C.c_int),
         "hgx_query_set_free": ([vp], None),
         "hgx_pattern_batch_set_into": ([vp, vp, vp, vp, i64, C.POINTER(i64), vp], C.c_int),
+        # include/hgx_paths.h
+        "hgx_link_weights_create": ([vp, vp, C.POINTER(vp)], C.c_int),
+        "hgx_link_weights_free": ([vp], None),
+        "hgx_shortest_paths": ([vp, vp, vp, i32, C.POINTER(AlgenOpts), vp, C.POINTER(vp)], C.c_int),
+        "hgx_sp_result_info": ([vp, C.POINTER(i32)], C.c_int),
+        "hgx_sp_result_distances": ([vp, vp, vp], C.c_int),
+        "hgx_sp_result_path": ([vp, i32, vp, vp, i64, C.POINTER(i64)], C.c_int),
+        "hgx_sp_result_distance_row": ([vp, i32, i64, i64, vp], C.c_int),
+        "hgx_sp_result_predecessor_row": ([vp, i32, i64, i64, vp, vp], C.c_int),
+        "hgx_sp_result_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+        "hgx_sp_result_free": ([vp], None),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

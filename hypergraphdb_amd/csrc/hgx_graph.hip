@@ -327,6 +327,7 @@ int hgx_graph_context(hgx_graph* g, hgx_graph** out) {
     c->seq_pack_min = g->seq_pack_min;
     c->xb_flat = g->xb_flat;
     c->xb_static = g->xb_static;
+    c->sp_budget_bytes = g->sp_budget_bytes;
     c->ranks_ordered = g->ranks_ordered; c->q_inline = g->q_inline;
     c->q_coalesce = g->q_coalesce; c->q_coalesce_max = g->q_coalesce_max;
     guard.c = nullptr;
@@ -577,6 +578,9 @@ int hgx_set_option(hgx_graph* g, int32_t option, int64_t value) {
         if (!g->shard) fail(HGX_E_INVALID, "hgx_set_option: HGX_OPT_XB_STATIC applies to partition shards");
         if (value < -1 || value > 2) fail(HGX_E_INVALID, "hgx_set_option: static broadcast mode outside -1..2");
         g->xb_static = (int32_t)value;
+    } else if (option == HGX_OPT_SP_BUDGET) {
+        if (value < 1) fail(HGX_E_INVALID, "hgx_set_option: shortest-path budget below 1 byte");
+        g->sp_budget_bytes = value;
     } else fail(HGX_E_INVALID, "hgx_set_option: unknown option");
     HGX_API_END
 }
