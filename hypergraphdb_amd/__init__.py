@@ -4,7 +4,8 @@ Native engine: libhgx.so (HIP kernels for gfx950 + the C ABI of include/hgx.h).
 This package is the host-side mirror of the reference interfaces on that path:
   snapshot.HyperGraphSnapshot   the store snapshot (bipartite CSR on the device)
   algorithms                    DefaultALGenerator / HGBreadthFirstTraversal / bfs_batch
-  query                         hg.and/type/incident/orderedLink, GpuAndToQuery, pattern_batch
+  query                         hg.and/or/type/incident/orderedLink, GpuAndToQuery, GpuOrToQuery, pattern_batch,
+                                pattern_batch_dnf (include/hgx_dnf.h)
   classics                      GraphClassics.dijkstra / shortest_paths (include/hgx_paths.h)
 """
 from ._lib import HGXError, HGXUnsupported, lib  # noqa: F401
@@ -12,8 +13,9 @@ from .algorithms import (AtomTypeCondition, BfsResult, DefaultALGenerator, HGBre
                          SequenceResult, bfs_sequence,
                          HGException, bfs_batch)
 from .classics import GraphClassics, LinkWeights, ShortestPathsResult, shortest_paths  # noqa: F401
-from .query import (ArityCondition, GpuAndToQuery, HGQueryConfiguration, LinkCondition,  # noqa: F401
-                    PositionedIncidentCondition, TypePlusCondition, find_all, hg, pattern_batch)
+from .query import (And, ArityCondition, GpuAndToQuery, GpuOrToQuery, HGQueryConfiguration, LinkCondition,  # noqa: F401
+                    Or, PositionedIncidentCondition, TypePlusCondition, find_all, hg, pattern_batch,
+                    pattern_batch_dnf, to_dnf)
 from .snapshot import HyperGraphSnapshot, export_store, rank_handles, read_snapshot, write_snapshot  # noqa: F401
 
 __version__ = "0.1.0"

@@ -82,6 +82,9 @@ EXPORTED_PATHS = (
     "hgx_sp_result_stats", "hgx_sp_result_free",
 )
 
+# Every symbol include/hgx_dnf.h declares (checked by tests/test_dnf_ref.py without a GPU).
+EXPORTED_DNF = ("hgx_pattern_batch_dnf", "hgx_query_result_union_stats")
+
 
 class GraphDesc(C.Structure):
     _fields_ = [("num_atoms", C.c_int64), ("num_links", C.c_int64), ("link_atom", C.c_void_p),
@@ -244,6 +247,10 @@ def lib():
         "hgx_sp_result_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
         "hgx_sp_result_free": ([vp], None),
+        # include/hgx_dnf.h
+        "hgx_pattern_batch_dnf": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)], C.c_int),
+        "hgx_query_result_union_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hgx_dnf.h"
 #include "../../include/hgx_paths.h"
 
 namespace hgx {
@@ -434,4 +435,27 @@ inline int grid_for(int64_t work_items, int block, int max_blocks = 8192) {
     int64_t b = ceil_div(work_items > 0 ? work_items : 1, block);
     return (int)(b < max_blocks ? b : max_blocks);
 }
+// The union stage of a DNF batch (hgx_union.hip) over the clause results the pattern
+// pipeline left in device memory.  Everything but the out_* pointers (the mapped result area) is device
+// memory; ctr is zeroed by the launcher.
+struct UnionArgs {
+    int32_t n_queries, n_clauses;
+    const int64_t* clause_off;   // [n_queries + 1] clauses of each query
+    const int64_t* run_off;      // [n_clauses + 1] hit offsets of each clause (hgx_q_place's result offsets)
+    const int32_t* hits;         // [cap] the clause hits, each clause ascending
+    int64_t cap;                 // workspace capacity in hits (the grids and the scan are sized from it)
+    const int64_t* stat;         // [8] statistics of the clause stage: [2] overflow
+    uint8_t* keep;               // [cap + 1] keep flags
+    int64_t* pre;                // [cap + 1] their exclusive prefix sum
+    void* tmp;                   // scan temporary storage (union_temp_bytes)
+    size_t tmp_bytes;
+    unsigned long long* ctr;     // [4] binary-search probes / runs visited of keep, of place
+    int64_t* out_stat;           // [8] mapped: the clause stage's statistics, [3] ids kept, [6] clause hits
+    unsigned long long* out_ctr; // [4] mapped: ctr
+    int64_t* out_off;            // [n_queries + 1] mapped: result offsets
+    int32_t* out_ids;            // [cap] mapped: result ids
+};
+size_t union_temp_bytes(int64_t cap, hipStream_t s);
+// Enqueues the union on s: no synchronisation, nothing read back by the host.
+void union_launch(const UnionArgs& a, hipStream_t s);
 }  // namespace hgx

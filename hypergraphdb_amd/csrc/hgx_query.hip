@@ -1066,6 +1066,9 @@ struct hgx_query_result {
     int64_t* ext_off = nullptr;
     int32_t* ext_ids = nullptr;
     int64_t ext_cap = 0, n_hits = 0;
+    // hgx_pattern_batch_dnf: clause hits before the union, ids kept, device ms and algorithmic bytes of it
+    int64_t clause_hits = 0, kept = 0;
+    double ms_union = 0, bytes_union = 0;
 };
 
 // A packed batch resident in device memory (hgx_query_set_create), in the staging layout of the
@@ -1106,6 +1109,10 @@ struct NormBatch {
     std::vector<int32_t> nop;
     std::vector<int32_t> anchors, types, pos, pattern;
     std::vector<int64_t> p_off{0};
+    // a DNF batch (hgx_pattern_batch_dnf): the queries normalised are the clauses of n_or Or queries,
+    // and an error names the Or query and the clause inside it
+    const int64_t* clause_off = nullptr;
+    int32_t n_or = 0;
 };
 
 template <class Get>
@@ -1119,7 +1126,11 @@ void normalise(hgx_graph* g, int32_t n, Get get, NormBatch& nb) {
     for (int32_t q = 0; q < n; ++q) {
         QueryIn in;
         get(q, in);
-        auto qs = [q] { return std::to_string(q); };   // built only on the error paths
+        auto qs = [q, &nb] {   // built only on the error paths
+            if (!nb.clause_off) return std::to_string(q);
+            const int64_t o = std::upper_bound(nb.clause_off, nb.clause_off + nb.n_or + 1, (int64_t)q) - nb.clause_off - 1;
+            return std::to_string(o) + " clause " + std::to_string(q - nb.clause_off[o]);
+        };
         if (in.n_types < 0 || in.n_inc < 0 || in.n_pos < 0 || in.n_pat < 0 || (in.n_types > 0 && !in.types) ||
             (in.n_inc > 0 && !in.inc) || (in.n_pos > 0 && !in.pos) || (in.n_pat > 0 && (!in.pat_off)) || in.arity < -1)
             fail(HGX_E_INVALID, "hgx_pattern_batch: bad query " + qs());
@@ -1351,6 +1362,11 @@ struct Front {
     int64_t* blk = nullptr;      // single-pass pipeline: [3 per block of 256 queries] candidates, bad, unsupported
     int64_t* lpre = nullptr;     //   [n] candidates of the queries before q in its block of 256
     u64* ctr = nullptr;          //   the match's counter shards, zeroed by the front kernel
+    // DNF batch (hgx_pattern_batch_dnf): the queries are clauses; clause_off_h [n_or + 1] goes up with the
+    // conditions (front_host) and the back end unions the clause results of each query on the device
+    int32_t n_or = -1;           //   Or queries of the batch (-1: a plain batch)
+    const int64_t* clause_off_h = nullptr;
+    const int64_t* clause_off = nullptr;   //   its device copy
 };
 
 // Buffers taken from the graph pool for one call, released on every exit path.
@@ -1370,6 +1386,7 @@ struct Scratch {
 struct Events {
     hgx_graph* g = nullptr;
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t u = nullptr;   // start of the union stage (DNF batches only: taken on first use)
     bool on = false;
     void init(hgx_graph* gg) {
         g = gg;
@@ -1385,9 +1402,22 @@ struct Events {
         }
     }
     void rec(int i, hipStream_t s) { if (on) HGX_HIP(hipEventRecord(e[i], s)); }
+    void rec_union(hipStream_t s) {
+        if (!on) return;
+        if (!u) {
+            if (!g->ev_pool.empty()) {
+                u = g->ev_pool.back();
+                g->ev_pool.pop_back();
+            } else {
+                HGX_HIP(hipEventCreate(&u));
+            }
+        }
+        HGX_HIP(hipEventRecord(u, s));
+    }
     ~Events() {
         for (int i = 0; i < 4; ++i)
             if (e[i]) g->ev_pool.push_back(e[i]);
+        if (u) g->ev_pool.push_back(u);
     }
 };
 
@@ -1412,6 +1442,7 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
                  o_types = u.take(bytes_of(nb.types)), o_pos = u.take(bytes_of(nb.pos)),
                  o_poff = u.take(bytes_of(nb.p_off)), o_pat = u.take(bytes_of(nb.pattern)),
                  o_nop = u.take(bytes_of(nb.nop));
+    const size_t o_cl = f.n_or >= 0 ? u.take(sizeof(int64_t) * ((size_t)f.n_or + 1)) : 0;
     char* h = (char*)g->pinned_buf(u.off);
     auto put = [&](size_t o, const auto& v) {
         if (!v.empty()) std::memcpy(h + o, v.data(), sizeof(v[0]) * v.size());
@@ -1423,6 +1454,7 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     put(o_poff, nb.p_off);
     put(o_pat, nb.pattern);
     put(o_nop, nb.nop);
+    if (f.n_or >= 0) std::memcpy(h + o_cl, f.clause_off_h, sizeof(int64_t) * ((size_t)f.n_or + 1));
     char* d = (char*)sc.take(u.off);
     f.plan = (QPlan*)sc.take(sizeof(QPlan) * n);
     f.nch = (int32_t*)sc.take(sizeof(int32_t) * (n + 1));
@@ -1435,6 +1467,7 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     f.pos = (const int32_t*)(d + o_pos);
     f.poff = (const int64_t*)(d + o_poff);
     f.pat = (const int32_t*)(d + o_pat);
+    if (f.n_or >= 0) f.clause_off = (const int64_t*)(d + o_cl);
     f.cond_bytes = 20.0 * nb.anchors.size() + 4.0 * nb.types.size() + 4.0 * nb.pos.size() +
                    4.0 * nb.pattern.size() + (double)sizeof(QDesc) * n;
     // the single-pass pipeline: the plan + per-block candidate totals
@@ -1560,9 +1593,12 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         int64_t* outoff = (int64_t*)w.take(sizeof(int64_t) * (capC + 1));
         u64* ctr = (u64*)w.take(sizeof(u64) * kQShards * kQStride);
         // result area in mapped host memory, written by the kernels (no copy back):
-        // stat[8] | ctr[4] | q_off[n+1] | ids[capK]
-        const size_t m_stat = 0, m_ctr = 64, m_qoff = 128;
-        const size_t m_ids = m_qoff + ((8 * (size_t)(n + 1) + 15) & ~(size_t)15);
+        // stat[8] | ctr[8] | q_off[nq+1] | ids[capK]      (a DNF batch: ctr[12], the union's four counters
+        // after the match's)
+        const bool dnf = f.n_or >= 0;
+        const int32_t nq = dnf ? f.n_or : n;   // queries of the result (a DNF batch: n counts its clauses)
+        const size_t m_stat = 0, m_ctr = 64, m_qoff = dnf ? 160 : 128;
+        const size_t m_ids = m_qoff + ((8 * (size_t)(nq + 1) + 15) & ~(size_t)15);
         char* hm = (char*)g->mapped_buf(m_ids + 4 * (size_t)capK);
         void* hmd = nullptr;
         HGX_HIP(hipHostGetDevicePointer(&hmd, hm, 0));
@@ -1571,6 +1607,30 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         u64* ctr_d = (u64*)(rd + m_ctr);
         int64_t* qoff_d = (int64_t*)(rd + m_qoff);
         int32_t* ids_d = (int32_t*)(rd + m_ids);
+        // DNF batch: the placement writes the clause hits, their offsets and its statistics into device
+        // memory instead (they never cross the host link); the union publishes the result area
+        UnionArgs un{};
+        if (dnf) {
+            un.n_queries = nq;
+            un.n_clauses = n;
+            un.clause_off = f.clause_off;
+            un.cap = capK;
+            un.out_stat = stat_d;
+            un.out_ctr = ctr_d + qNum;
+            un.out_off = qoff_d;
+            un.out_ids = ids_d;
+            stat_d = (int64_t*)w.take(sizeof(int64_t) * 8);
+            qoff_d = (int64_t*)w.take(sizeof(int64_t) * ((size_t)n + 1));
+            ids_d = (int32_t*)w.take(sizeof(int32_t) * (size_t)capK);
+            un.stat = stat_d;
+            un.run_off = qoff_d;
+            un.hits = ids_d;
+            un.keep = (uint8_t*)w.take((size_t)capK + 1);
+            un.pre = (int64_t*)w.take(sizeof(int64_t) * ((size_t)capK + 1));
+            un.tmp_bytes = union_temp_bytes(capK, s);
+            un.tmp = w.take(un.tmp_bytes);
+            un.ctr = (u64*)w.take(sizeof(u64) * 4);
+        }
         const int64_t nbp = std::max<int64_t>(1, ceil_div(capC, kPlaceChunks));
         // derived flat index: no scan launch between the front kernel and the match (its counter shards
         // were zeroed by the front kernel; a re-run after a workspace overflow zeroes them here)
@@ -1579,7 +1639,7 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         // without timing events the host waits on a completion flag the placement writes into the result
         // area (stat[7]) instead of asking the stream (each hipStreamQuery costs a few microseconds)
         static const bool stream_wait = ab_env("HGX_Q_STREAM_WAIT") != nullptr;   // A/B
-        const bool flag = derived && !ev.on && !stream_wait;
+        const bool flag = derived && !ev.on && !stream_wait && !dnf;
         u64 flag_seq = 0;
         if (flag) {
             if (!g->q_ticket) {
@@ -1627,6 +1687,10 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
                                                              0, 0, 0, nullptr, 0);
             HGX_CHECK_LAUNCH();
         }
+        if (dnf) {
+            ev.rec_union(s);
+            union_launch(un, s);
+        }
         ev.rec(3, s);
         if (flag) {
             const u64* fl = (const u64*)(hm + m_stat) + 7;
@@ -1658,11 +1722,28 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         const int64_t total = stat[3];
         r->n_hits = total;
         if (r->ext_off) {   // caller buffers: no result vectors
-            std::memcpy(r->ext_off, qoff_h, sizeof(int64_t) * (n + 1));
+            std::memcpy(r->ext_off, qoff_h, sizeof(int64_t) * (nq + 1));
             if (total <= r->ext_cap && total > 0) std::memcpy(r->ext_ids, ids_h, sizeof(int32_t) * total);
         } else {
-            std::memcpy(r->offsets.data(), qoff_h, sizeof(int64_t) * (n + 1));
+            std::memcpy(r->offsets.data(), qoff_h, sizeof(int64_t) * (nq + 1));
             r->ids.assign(ids_h, ids_h + total);
+        }
+        if (dnf) {
+            // algorithmic bytes of the union: per clause hit its id, its flag written, read
+            // by the scan and by the placement, and its 8-byte prefix; per kept id the id read and written;
+            // 4 B per binary-search probe; 16 B (two run offsets) per run visited, + 16 B (two prefixes)
+            // in the placement; the clause and query offset tables once, + the query offsets written
+            const u64* uc = ctr_h + qNum;
+            r->clause_hits = stat[6];
+            r->kept = total;
+            r->bytes_union = 15.0 * (double)stat[6] + 8.0 * (double)total + 4.0 * ((double)uc[0] + (double)uc[2]) +
+                             16.0 * (double)uc[1] + 32.0 * (double)uc[3] + 8.0 * ((double)n + 1) +
+                             24.0 * ((double)nq + 1);
+            if (ev.on) {
+                float c = 0;
+                HGX_HIP(hipEventElapsedTime(&c, ev.u, ev.e[3]));
+                r->ms_union = c;
+            }
         }
         if (prof)
             std::fprintf(stderr, "[hgx query] single-pass n=%d host+device %.3f ms (chunks %lld, candidates %lld, hits %lld)\n",
@@ -1726,6 +1807,35 @@ int run_batch_with(hgx_graph* g, int32_t n, hgx_query_result** out, FrontFn fron
 
 int run_batch(hgx_graph* g, int32_t n, NormBatch& nb, hgx_query_result** out) {
     return run_batch_with(g, n, out, [&](Scratch& sc, Events& ev, Front& f) { front_host(g, n, nb, sc, ev, f); });
+}
+
+// A DNF batch: the n clauses of nb run through the same front and back end, whose placement leaves the
+// clause hits in device memory; the union stage (hgx_union.hip) writes the n_or results.  Takes the graph
+// mutex itself, like run_batch_with (no cross-thread coalescing).
+int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t n, NormBatch& nb,
+                  hgx_query_result** out) {
+    HGX_API_BEGIN
+    const bool prof = trace_env("HGX_QUERY_PROFILE");
+    const double t0 = now_ms();
+    std::unique_ptr<hgx_query_result> r(new hgx_query_result());
+    r->n = n_or;
+    r->offsets.assign((size_t)n_or + 1, 0);
+    if (n > 0) {
+        std::lock_guard<std::mutex> lk(g->mu);
+        HGX_HIP(hipSetDevice(g->device));
+        ensure_type_grouped(g);
+        ensure_ts_inline(g);
+        Scratch sc{g, {}};
+        Events ev;
+        ev.init(g);
+        Front f;
+        f.n_or = n_or;
+        f.clause_off_h = clause_off;
+        front_host(g, n, nb, sc, ev, f);
+        back_end(g, n, f, sc, ev, r.get(), prof, t0);
+    }
+    *out = r.release();
+    HGX_API_END
 }
 
 int run_batch_packed_direct(hgx_graph* g, int32_t n, const int32_t* type, const int64_t* inc_off, const int32_t* inc,
@@ -1951,6 +2061,56 @@ int hgx_query_result_ms(const hgx_query_result* r, double* ms_total, double* ms_
 }
 
 void hgx_query_result_free(hgx_query_result* r) { delete r; }
+
+int hgx_pattern_batch_dnf(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
+                          const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
+                          const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
+                          const int32_t* arity, hgx_query_result** out) {
+    HGX_API_BEGIN
+    if (!g || !out || n_queries < 0 || !clause_off) fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: bad argument");
+    *out = nullptr;
+    if (clause_off[0] != 0) fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: clause_off[0] is not 0");
+    for (int32_t q = 0; q < n_queries; ++q)
+        if (clause_off[q + 1] < clause_off[q])
+            fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: clause_off decreases at query " + std::to_string(q));
+    const int64_t nc = clause_off[n_queries];
+    if (nc > (int64_t)INT32_MAX - 1) fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch_dnf: too many clauses");
+    if (nc > 0 && (!type_off || !inc_off || !pos_off || !pset_off || !arity))
+        fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: bad argument");
+    if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch_dnf: not available on a partition shard");
+    const int32_t n = (int32_t)nc;
+    NormBatch nb;
+    nb.clause_off = clause_off;
+    nb.n_or = n_queries;
+    normalise(g, n,
+              [&](int32_t q, QueryIn& in) {
+                  in.n_types = (int32_t)(type_off[q + 1] - type_off[q]);
+                  in.types = types ? types + type_off[q] : nullptr;
+                  in.n_inc = (int32_t)(inc_off[q + 1] - inc_off[q]);
+                  in.inc = inc ? inc + inc_off[q] : nullptr;
+                  in.n_pos = (int32_t)(pos_off[q + 1] - pos_off[q]);
+                  in.pos = pos ? pos + 4 * pos_off[q] : nullptr;
+                  in.n_pat = (int32_t)(pset_off[q + 1] - pset_off[q]);
+                  if (in.n_pat > 0 && !pat_off) fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: null pat_off");
+                  in.pat_off = pat_off ? pat_off + pset_off[q] : nullptr;
+                  in.pat = pat;
+                  in.arity = arity[q];
+              },
+              nb);
+    return run_batch_dnf(g, n_queries, clause_off, n, nb, out);
+    HGX_API_END
+}
+
+int hgx_query_result_union_stats(const hgx_query_result* r, int64_t* clause_hits, int64_t* kept, double* ms_union,
+                                 double* bytes_union) {
+    HGX_API_BEGIN
+    if (!r) fail(HGX_E_INVALID, "hgx_query_result_union_stats: null result");
+    if (clause_hits) *clause_hits = r->clause_hits;
+    if (kept) *kept = r->kept;
+    if (ms_union) *ms_union = r->ms_union;
+    if (bytes_union) *bytes_union = r->bytes_union;
+    HGX_API_END
+}
 
 int hgx_query_coalesce_stats(hgx_graph* g, int64_t* device_batches, int64_t* caller_batches) {
     HGX_API_BEGIN

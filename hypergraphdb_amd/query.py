@@ -10,6 +10,9 @@ Reference (C = core/src/java/org/hypergraphdb):
     nested And and adding incident(x) for every non-ANY orderedLink target.
   * SubsumedCondition / SubsumesCondition -> BFS over HGSubsumes links
     (C/query/cond2qry/ToQueryMap.java:282-370).
+  * hg.or: ExpressionBasedQuery.toDNF (ExpressionBasedQuery.java:94-167) turns any And / Or tree into an Or
+    of Ands; OrToQuery (C/query/cond2qry/OrToQuery.java:14-43) chains UnionResults
+    (C/query/impl/UnionResult.java).  Here: to_dnf + pattern_batch_dnf (one device call, include/hgx_dnf.h).
 """
 from __future__ import annotations
 
@@ -56,6 +59,12 @@ class OrderedLinkCondition:
             i += 1
         return j == len(self.targets)
 
+    def __eq__(self, o):
+        return isinstance(o, OrderedLinkCondition) and o.targets == self.targets
+
+    def __hash__(self):
+        return hash(("orderedLink", self.targets))
+
     def __repr__(self):
         return f"orderedLink{self.targets}"
 
@@ -69,6 +78,12 @@ class LinkCondition:
         if len(targets) == 1 and isinstance(targets[0], (list, tuple, set)):
             targets = tuple(targets[0])
         self.targets = tuple(int(t) for t in targets)
+
+    def __eq__(self, o):
+        return isinstance(o, LinkCondition) and o.targets == self.targets
+
+    def __hash__(self):
+        return hash(("link", self.targets))
 
     def __repr__(self):
         return f"links{self.targets}"
@@ -87,6 +102,12 @@ class PositionedIncidentCondition:
     def record(self):
         return (self.target, self.lower, self.upper, int(self.complement))
 
+    def __eq__(self, o):
+        return isinstance(o, PositionedIncidentCondition) and o.record() == self.record()
+
+    def __hash__(self):
+        return hash(("incidentAt",) + self.record())
+
     def __repr__(self):
         return f"incidentAt({self.target},{self.lower},{self.upper},{self.complement})"
 
@@ -96,6 +117,12 @@ class ArityCondition:
 
     def __init__(self, arity):
         self.arity = int(arity)
+
+    def __eq__(self, o):
+        return isinstance(o, ArityCondition) and o.arity == self.arity
+
+    def __hash__(self):
+        return hash(("arity", self.arity))
 
     def __repr__(self):
         return f"arity({self.arity})"
@@ -121,6 +148,12 @@ class TypePlusCondition:
         r.close()
         return cls(key_of_atom[a] for a in atoms if a in key_of_atom)
 
+    def __eq__(self, o):
+        return isinstance(o, TypePlusCondition) and o.types == self.types
+
+    def __hash__(self):
+        return hash(("typePlus", self.types))
+
     def __repr__(self):
         return f"typePlus{sorted(self.types)}"
 
@@ -128,6 +161,13 @@ class TypePlusCondition:
 class And(list):
     def __repr__(self):
         return "and(" + ", ".join(map(repr, self)) + ")"
+
+
+class Or(list):
+    """hg.or(...) (C/query/Or.java): a link atom matching at least one operand."""
+
+    def __repr__(self):
+        return "or(" + ", ".join(map(repr, self)) + ")"
 
 
 class MapCondition:
@@ -199,6 +239,10 @@ class hg:
     @staticmethod
     def and_(*conds):
         return And(conds)
+
+    @staticmethod
+    def or_(*conds):
+        return Or(conds)
 
     @staticmethod
     def bfs(start, link_predicate=None, return_preceding=True, return_succeeding=True, reverse_order=False):
@@ -275,9 +319,54 @@ def _from_tuple(q):
             "patterns": [] if pat is None else [tuple(pat)], "arity": -1}
 
 
+MAX_DNF_CLAUSES = 4096
+
+
+def to_dnf(cond) -> "Or":
+    """ExpressionBasedQuery.toDNF (ExpressionBasedQuery.java:94-167) + the part of simplify that matters
+    here: the condition as an Or of Ands of leaf conditions.  Nested And / Or are flattened (:106-111,
+    :144-149), And is distributed over Or (:112-125), a sub-condition repeated inside a clause and a clause
+    repeated inside the Or are dropped (the HashSets of :100 and :138).  A clause that normalize() reports
+    as "empty" (it can match nothing) is dropped, as simplify removes Nothing from an Or.  A clause holding
+    anything but the accelerated leaves raises HGXUnsupported, and so do more than MAX_DNF_CLAUSES clauses
+    (the distribution is exponential; the caller falls back to the CPU's OrToQuery)."""
+    def cap(clauses):
+        if len(clauses) > MAX_DNF_CLAUSES:
+            raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"more than {MAX_DNF_CLAUSES} clauses in the DNF of {cond!r}")
+        return clauses
+
+    def dedupe(clauses):
+        seen, out = set(), []
+        for c in clauses:
+            k = frozenset(c)
+            if k not in seen:
+                seen.add(k)
+                out.append(c)
+        return out
+
+    def dnf(c):   # -> list of clauses, a clause = tuple of distinct leaves in first-seen order
+        if isinstance(c, And):
+            acc = [()]
+            for sub in c:
+                acc = cap(dedupe([a + tuple(x for x in b if x not in a) for a in acc for b in dnf(sub)]))
+            return acc
+        if isinstance(c, Or):
+            acc = []
+            for sub in c:
+                acc = cap(dedupe(acc + dnf(sub)))
+            return acc
+        if not isinstance(c, _LEAVES):
+            raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"shape not accelerated: {c!r}")
+        return [(c,)]
+
+    return Or(And(cl) for cl in dnf(cond) if normalize(And(cl)) != "empty")
+
+
 class QueryResult:
-    def __init__(self, offsets, ids, ms=None):
+    def __init__(self, offsets, ids, ms=None, union=None):
         self.offsets, self.ids, self.ms = offsets, ids, ms
+        # pattern_batch_dnf: {"clause_hits", "kept", "ms_union", "bytes_union"} (hgx_query_result_union_stats)
+        self.union = union
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -384,24 +473,14 @@ def pattern_batch_ext_arrays(snapshot, type_off, types, inc_off, inc, pos_off, p
     return QueryResult(off, ids[: int(off[-1])], {"ms_total": a.value, "ms_match": b.value, "bytes_match": c.value})
 
 
-def pattern_batch(snapshot, queries) -> QueryResult:
-    """Evaluate many accelerated And queries in one GPU launch sequence.  ``queries``: conditions,
-    normalised dicts, or legacy (type, incident, pattern) tuples (pattern None = no orderedLink)."""
-    norm = []
-    for q in queries:
-        if isinstance(q, tuple):
-            q = _from_tuple(q)
-        elif not isinstance(q, dict) and q != "empty":
-            q = normalize(q)
-        norm.append(q)
+def _ext_arrays(norm):
+    """normalised dicts (or "empty") -> the flat arrays of hgx_pattern_batch_ext, in its argument order"""
     n = len(norm)
     type_off, inc_off, pos_off, pset_off = (np.zeros(n + 1, np.int64) for _ in range(4))
     types, inc, pos, pat, pat_off = [], [], [], [], [0]
     arity = np.full(n, -1, np.int32)
-    empty = np.zeros(n, bool)
     for i, q in enumerate(norm):
         if q == "empty":   # nothing can match: run a NOP (an empty orderedLink) on a valid anchor
-            empty[i] = True
             q = {"types": [], "inc": [0], "pos": [], "patterns": [()], "arity": -1}
         types.extend(q["types"])
         type_off[i + 1] = len(types)
@@ -415,9 +494,61 @@ def pattern_batch(snapshot, queries) -> QueryResult:
             pat_off.append(len(pat))
         pset_off[i + 1] = len(pat_off) - 1
         arity[i] = q["arity"]
-    r = pattern_batch_ext_arrays(snapshot, type_off, np.array(types or [0], np.int32), inc_off,
-                                 np.array(inc or [0], np.int32), pos_off, np.array(pos or [0], np.int32), pset_off,
-                                 np.array(pat_off, np.int64), np.array(pat or [0], np.int32), arity)
+    return (type_off, np.array(types or [0], np.int32), inc_off, np.array(inc or [0], np.int32), pos_off,
+            np.array(pos or [0], np.int32), pset_off, np.array(pat_off, np.int64), np.array(pat or [0], np.int32),
+            arity)
+
+
+def pattern_batch_dnf_arrays(snapshot, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off,
+                             pat, arity) -> QueryResult:
+    """Flat DNF batch for hgx_pattern_batch_dnf (include/hgx_dnf.h): query q = Or over the clauses
+    [clause_off[q], clause_off[q+1]) of the hgx_pattern_batch_ext arrays."""
+    clause_off = np.ascontiguousarray(clause_off, np.int64)
+    n = len(clause_off) - 1
+    arrs = [np.ascontiguousarray(type_off, np.int64), np.ascontiguousarray(types, np.int32),
+            np.ascontiguousarray(inc_off, np.int64), np.ascontiguousarray(inc, np.int32),
+            np.ascontiguousarray(pos_off, np.int64), np.ascontiguousarray(pos, np.int32),
+            np.ascontiguousarray(pset_off, np.int64), np.ascontiguousarray(pat_off, np.int64),
+            np.ascontiguousarray(pat, np.int32), np.ascontiguousarray(arity, np.int32)]
+    h = C.c_void_p()
+    check(lib().hgx_pattern_batch_dnf(snapshot.handle, n, clause_off.ctypes.data, *(a.ctypes.data for a in arrs),
+                                      C.byref(h)))
+    ch, kept, ms_u, by_u = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    rc = lib().hgx_query_result_union_stats(h, C.byref(ch), C.byref(kept), C.byref(ms_u), C.byref(by_u))
+    r = _read_result(h, n)   # frees the result
+    check(rc)
+    r.union = {"clause_hits": ch.value, "kept": kept.value, "ms_union": ms_u.value, "bytes_union": by_u.value}
+    return r
+
+
+def pattern_batch_dnf(snapshot, queries) -> QueryResult:
+    """Evaluate many And / Or trees over the accelerated leaves in one device call: every query goes
+    through to_dnf, its clauses run as one hgx_pattern_batch_ext-shaped batch and are united on the device
+    (ascending, each link atom once).  ``queries``: conditions, or lists of normalised clause dicts.
+    ``result.union`` holds the union statistics."""
+    clause_off, norm = [0], []
+    for q in queries:
+        if type(q) in (list, tuple):
+            norm.extend(q)
+        else:
+            norm.extend(normalize(c) for c in to_dnf(q))
+        clause_off.append(len(norm))
+    return pattern_batch_dnf_arrays(snapshot, clause_off, *_ext_arrays(norm))
+
+
+def pattern_batch(snapshot, queries) -> QueryResult:
+    """Evaluate many accelerated And queries in one GPU launch sequence.  ``queries``: conditions,
+    normalised dicts, or legacy (type, incident, pattern) tuples (pattern None = no orderedLink)."""
+    norm = []
+    for q in queries:
+        if isinstance(q, tuple):
+            q = _from_tuple(q)
+        elif not isinstance(q, dict) and q != "empty":
+            q = normalize(q)
+        norm.append(q)
+    n = len(norm)
+    empty = np.array([q == "empty" for q in norm], bool)
+    r = pattern_batch_ext_arrays(snapshot, *_ext_arrays(norm))
     if empty.any():
         parts = [np.empty(0, np.int32) if empty[i] else r[i] for i in range(n)]
         off = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
@@ -449,6 +580,29 @@ class GpuAndToQuery:
         return QueryMetaData(True, True, -1)
 
 
+class GpuOrToQuery:
+    """ConditionToQuery for Or (and for an And holding an Or), registered with
+    HGQueryConfiguration.addCompiler(Or, ...): the condition's DNF as one device batch."""
+
+    def getQuery(self, snapshot, cond):
+        clauses = [normalize(c) for c in to_dnf(cond)]
+
+        class _Q:
+            def execute(_self):
+                return list(pattern_batch_dnf(snapshot, [clauses])[0].tolist())
+
+        return _Q()
+
+    def getMetaData(self, snapshot, cond):
+        """OrToQuery.getMetaData (OrToQuery.java:44-76): ordered and random-access when every operand
+        is -- every accelerated clause is (GpuAndToQuery.getMetaData)."""
+        try:
+            to_dnf(cond)
+        except HGXUnsupported:
+            return QueryMetaData(False, False, -1)
+        return QueryMetaData(True, True, -1)
+
+
 class HGQueryConfiguration:
     """Per-graph compiler registry (C/query/HGQueryConfiguration.java:37-66)."""
 
@@ -462,6 +616,10 @@ class HGQueryConfiguration:
         return self._compilers.get(cls)
 
 
+def _has_or(cond):
+    return isinstance(cond, Or) or (isinstance(cond, And) and any(_has_or(c) for c in cond))
+
+
 def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
     """hg.findAll(graph, cond) for the accelerated shapes."""
     if isinstance(cond, BFSCondition):
@@ -472,6 +630,21 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
         return seq.pairs(0)[1].tolist()
     if isinstance(cond, MapCondition):
         return sorted({v for v in (cond.mapping(x) for x in find_all(snapshot, cond.cond, config)) if v is not None})
+    if isinstance(cond, Or) or (isinstance(cond, And) and _has_or(cond)):
+        compiler = (config.compiler(Or) if config else None) or GpuOrToQuery()
+        try:
+            return compiler.getQuery(snapshot, cond).execute()
+        except HGXUnsupported:
+            pass   # a part the pattern engine does not take (Map / BFS sub-conditions): host set algebra
+        if isinstance(cond, Or):
+            return sorted(set().union(*(find_all(snapshot, c, config) for c in cond)))
+        subs = _flatten(cond, [])
+        own = (MapCondition, BFSCondition, Or)
+        sets = [set(find_all(snapshot, c, config)) for c in subs if isinstance(c, own)]
+        rest = [c for c in subs if not isinstance(c, own)]
+        if rest:
+            sets.append(set(find_all(snapshot, And(rest), config)))
+        return sorted(set.intersection(*sets))
     if isinstance(cond, And):
         subs = _flatten(cond, [])
         if any(isinstance(c, (MapCondition, BFSCondition)) for c in subs):
