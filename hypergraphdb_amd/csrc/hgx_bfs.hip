@@ -261,6 +261,82 @@ __device__ __forceinline__ void block_add_sh(u64* stats, int c, u64 v) {
     }
 }
 
+// Fused level counts (HGX_OPT_COUNT_FUSED): a kernel that stores a level's new row also adds it into
+// per-source counts of its workgroup, so the readout needs no pass over the level's rows.  The counts
+// are bit-sliced in LDS: plane p, word w holds bit p of the counts of sources w*64 .. w*64+63.  A lane
+// adds its row word c by rippling the carry up the planes, one atomic exchange-or per plane:
+//   old = atomicXor(&P[p][w], c); c &= old; ++p;   until c == 0.
+// Every step keeps sum_p 2^p popcount(P[p]) + 2^p popcount(carry in flight) unchanged, so the sum is
+// exact under any interleaving of lanes and waves and needs no barrier.  Per-lane state is one row
+// part at most (fuse_add_cs; the carry-save planes of count_rows_body do not fit: the pull kernels
+// sit a few VGPRs under their occupancy step).  kFusePlanes planes hold < 2^24 rows per
+// workgroup (the host checks its grids against that, fuse_rows_ok); the plane bound keeps a row count
+// beyond it inside the array (the count would wrap, never write out of bounds).  At the end of the
+// kernel thread j folds source j's count out of the planes into the block's partial row, the layout
+// hgx_count_reduce reads: uint32 part[block][W*64].  Every block stores its row (zeros included).
+constexpr int kFusePlanes = 24;
+template <int W>
+__device__ __forceinline__ void fuse_zero(u64* P, unsigned int* done) {
+    for (int j = threadIdx.x; j < kFusePlanes * W; j += blockDim.x) P[j] = 0ull;
+    if (threadIdx.x == 0) *done = 0u;
+    __syncthreads();
+}
+// x added at plane p0 (weight 2^p0); the two words of a lane ripple together, so their LDS round
+// trips overlap
+template <int W>
+__device__ __forceinline__ void fuse_add(u64* P, int sub, typename Vec<Lay<W>::WPL>::T x, int p0 = 0) {
+    if constexpr (Lay<W>::WPL == 1) {
+        u64 c = x;
+        for (int p = p0; c != 0ull && p < kFusePlanes; ++p) c &= atomicXor(&P[p * W + sub], c);
+    } else {
+        u64 c0 = x.x, c1 = x.y;
+        for (int p = p0; (c0 | c1) != 0ull && p < kFusePlanes; ++p) {
+            u64 o0 = 0ull, o1 = 0ull;
+            if (c0) o0 = atomicXor(&P[p * W + sub * 2], c0);
+            if (c1) o1 = atomicXor(&P[p * W + sub * 2 + 1], c1);
+            c0 &= o0;
+            c1 &= o1;
+        }
+    }
+}
+// One carry-save level in the lane's registers in front of the planes (a lane always holds the same
+// words of its rows): `ones` takes the row, only the carry -- the bits this lane has now seen twice --
+// goes to plane 1.  Sparse rows (a level-1 row of config 2 has ~1.2 source bits) then rarely touch
+// LDS at all; fuse_flush adds what `ones` still holds to plane 0 before fuse_store.
+template <int W>
+__device__ __forceinline__ void fuse_add_cs(u64* P, int sub, typename Vec<Lay<W>::WPL>::T& ones,
+                                            typename Vec<Lay<W>::WPL>::T x) {
+    typedef Vec<Lay<W>::WPL> V;
+    const typename V::T carry = ones & x;
+    ones = ones ^ x;
+    if (V::nz(carry)) fuse_add<W>(P, sub, carry, 1);
+}
+template <int W>
+__device__ __forceinline__ void fuse_flush(u64* P, int sub, typename Vec<Lay<W>::WPL>::T ones) {
+    fuse_add<W>(P, sub, ones, 0);
+}
+// End of kernel, every lane of the wave active.  No block barrier: the waves of a pull finish far apart
+// (power-law degrees) and a wave waiting at a barrier keeps its registers from the next workgroup.
+// Each wave counts itself in *done (a shared word of its own, zeroed by fuse_zero) once its adds have
+// returned -- a ripple step waits for its atomic's result -- and the last one folds the planes P[0 ..
+// kFusePlanes * W) into the block's partial row.
+template <int W>
+__device__ __forceinline__ void fuse_store(const u64* P, unsigned int* done, uint32_t* __restrict__ part) {
+    __threadfence_block();
+    unsigned int last = 0;
+    if ((threadIdx.x & 63) == 0) last = atomicAdd(done, 1u) == (blockDim.x >> 6) - 1u;
+    last = (unsigned int)__shfl((int)last, 0);
+    if (!last) return;   // wave-uniform
+    __threadfence_block();
+    for (int j = threadIdx.x & 63; j < W * 64; j += 64) {   // j < W * 64: w < W, p < kFusePlanes
+        const int w = j >> 6, b = j & 63;
+        uint32_t n = 0;
+#pragma unroll
+        for (int p = 0; p < kFusePlanes; ++p) n |= (uint32_t)((P[p * W + w] >> b) & 1ull) << p;
+        part[(int64_t)blockIdx.x * (W * 64) + j] = n;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Link gather: lf[L] = OR_{v in targets(L), fa_d(v)} lvl_d[v]; la(L) set iff the row was written.
 // A wave owns 64 consecutive link rows (one la word); a G-lane group handles one row at a time.
@@ -712,17 +788,21 @@ hgx_link_gather2_o5(int64_t M, const int64_t* __restrict__ tgt_off, const int32_
 }
 
 template <int W, int JBX, bool SORT, int KR>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KR < Lay<W>::G ? 4 : 1, 8))) hgx_atom_pull2(int64_t A, const int64_t* __restrict__ inc_off,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KR < Lay<W>::G ? 4 : 3, 8))) hgx_atom_pull2(int64_t A, const int64_t* __restrict__ inc_off,
                                                       const int32_t* __restrict__ inc_row,
                                                       const u64* __restrict__ la, const u64* __restrict__ lf,
                                                       u64* __restrict__ vis, u64* __restrict__ ever,
                                                       u64* __restrict__ full, u64* __restrict__ lvl_next,
                                                       u64* __restrict__ fa_next, u64* __restrict__ ctr, FullMask fm,
-                                                      int flags, const u64* __restrict__ own) {
+                                                      int flags, const u64* __restrict__ own,
+                                                      uint32_t* __restrict__ cpart) {
     constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G, PW = Lay<W>::PER_WAVE;
     constexpr int JB = G >= 8 ? JBX : G;   // atoms of a group interleaved at once (register budget)
     static_assert(G >= 4, "pull2 needs G >= 4");
     typedef Vec<WPL> V;
+    __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
+    __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
+    if (cpart) fuse_zero<W>(cplanes, &cdone);
     const bool early = flags & 2, skip_full = flags & 4, all_rows = flags & kAllRows;
     const bool nt_idx = flags & kNtIdx, nt_out = flags & kNtOut;
     const int lane = threadIdx.x & 63, g = lane / G, sub = lane & (G - 1), base = lane & ~(G - 1);
@@ -730,7 +810,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KR < L
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
     const int64_t nwave = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const typename V::T FULL = full_part<W>(fm, sub);
-    u64 n_inc = 0, n_vis = 0, n_new = 0, n_newdeg = 0, n_newdeg_nf = 0, n_full = 0;
+    // per-lane statistics in 32 bits (6 VGPRs fewer, which pay for `cones`): a wave takes at most 2^11
+    // tiles (< 2^31 atoms over 2^14 waves; one tile when the grid is smaller), a lane group G <= 8
+    // light atoms of a tile, each of degree <= kHeavyDegree = 2^9: every sum stays below 2^24
+    uint32_t n_inc = 0, n_vis = 0, n_new = 0, n_newdeg = 0, n_newdeg_nf = 0, n_full = 0;
+    typename V::T cones = V::zero();   // fused counts: the lane's carry-save level
     for (int64_t tile = wave; tile * 64 < A; tile += nwave) {
         const u64 ever_w = ever[tile], full_w = full[tile];
         // partition part: a ghost's new row is partial and its vis / ever are rewritten by the
@@ -843,7 +927,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KR < L
                         if ((own_w >> pos) & 1ull) st_row<V>(vis + t * W + sub * WPL, old[jj] | nw, nt_out);
                         isnew = true;
                         becomes_full = group_all<G>(V::eq(old[jj] | nw, FULL));
-                        if (sub == 0) { n_newdeg += (u64)dj[jj]; if (!becomes_full) n_newdeg_nf += (u64)dj[jj]; }
+                        if (sub == 0) { n_newdeg += (uint32_t)dj[jj]; if (!becomes_full) n_newdeg_nf += (uint32_t)dj[jj]; }
+                        if (cpart) fuse_add_cs<W>(cplanes, sub, cones, nw);   // lane-divergent ripple: no shuffle inside
                     }
                 }
                 if (sub == 0) {   // the atom's own bit (slots are permuted: no ballot compression)
@@ -876,6 +961,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KR < L
     wave_add_sh(ctr + cNewAtoms, n_new);
     wave_add_sh(ctr + cNewDeg, n_newdeg);
     wave_add_sh(ctr + cNewDegNF, n_newdeg_nf);
+    if (cpart) {
+        fuse_flush<W>(cplanes, sub, cones);
+        fuse_store<W>(cplanes, &cdone, cpart);
+    }
 }
 
 // pull_range for the symmetric mode, G >= 4, restructured for memory-level parallelism: a group
@@ -992,9 +1081,13 @@ __global__ void __launch_bounds__(256) hgx_hub_finalize(int64_t H, const int32_t
                                                         u64* __restrict__ hubacc, u64* __restrict__ vis,
                                                         u64* __restrict__ ever, u64* __restrict__ full,
                                                         u64* __restrict__ lvl_next, u64* __restrict__ fa_next,
-                                                        u64* __restrict__ ctr, FullMask fm) {
+                                                        u64* __restrict__ ctr, FullMask fm,
+                                                        uint32_t* __restrict__ cpart) {
     constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G;
     typedef Vec<WPL> V;
+    __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
+    __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
+    if (cpart) fuse_zero<W>(cplanes, &cdone);
     const int sub = threadIdx.x & (G - 1);
     const int64_t grp = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
     const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) / G;
@@ -1021,6 +1114,7 @@ __global__ void __launch_bounds__(256) hgx_hub_finalize(int64_t H, const int32_t
             n_full += becomes_full;
             { const u64 dg_ = (u64)(inc_off[t + 1] - inc_off[t]); n_newdeg += dg_; if (!becomes_full) n_newdeg_nf += dg_; }
         }
+        if (cpart) fuse_add<W>(cplanes, sub, nw);
     }
     wave_add_sh(ctr + cNewFull, n_full);
     wave_add_sh(ctr + cAccHub, n_acc);
@@ -1028,6 +1122,7 @@ __global__ void __launch_bounds__(256) hgx_hub_finalize(int64_t H, const int32_t
     wave_add_sh(ctr + cNewAtoms, n_new);
     wave_add_sh(ctr + cNewDeg, n_newdeg);
     wave_add_sh(ctr + cNewDegNF, n_newdeg_nf);
+    if (cpart) fuse_store<W>(cplanes, &cdone, cpart);
 }
 
 // Sparse levels: mark every (typed) link incident to a frontier atom.  One wave per frontier word:
@@ -1829,7 +1924,7 @@ __global__ void __launch_bounds__(256) hgx_nonfull_list(int64_t A, const u64* __
 }
 
 template <int W>
-__global__ void __launch_bounds__(256) hgx_nf_pull(const int32_t* __restrict__ list, const u64* __restrict__ n_list,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) hgx_nf_pull(const int32_t* __restrict__ list, const u64* __restrict__ n_list,
                                                    const int64_t* __restrict__ inc_off,
                                                    const int32_t* __restrict__ inc_row,
                                                    const int32_t* __restrict__ inc_type, int32_t want_type,
@@ -1838,10 +1933,14 @@ __global__ void __launch_bounds__(256) hgx_nf_pull(const int32_t* __restrict__ l
                                                    const u64* __restrict__ lvl, u64* __restrict__ vis,
                                                    u64* __restrict__ ever, u64* __restrict__ full,
                                                    u64* __restrict__ lvl_next, u64* __restrict__ fa_next,
-                                                   u64* __restrict__ ctr, FullMask fm, int flags) {
+                                                   u64* __restrict__ ctr, FullMask fm, int flags,
+                                                   uint32_t* __restrict__ cpart) {
     constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G;
     static_assert(G >= 4, "nf pull needs G >= 4");
     typedef Vec<WPL> V;
+    __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
+    __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
+    if (cpart) fuse_zero<W>(cplanes, &cdone);
     const bool early = flags & 2;
     const int lane = threadIdx.x & 63, sub = lane & (G - 1), base = lane & ~(G - 1);
     const u64 gmask = (1ull << G) - 1ull;
@@ -1849,6 +1948,7 @@ __global__ void __launch_bounds__(256) hgx_nf_pull(const int32_t* __restrict__ l
     const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) / G;
     const typename V::T FULL = full_part<W>(fm, sub);
     const int64_t n = (int64_t)*n_list;
+    typename V::T cones = V::zero();   // fused counts: the lane's carry-save level
     u64 n_cand = 0, n_ent = 0, n_pins = 0, n_rows = 0, n_vis = 0, n_new = 0, n_newdeg = 0, n_newdeg_nf = 0,
         n_full = 0;
     for (int64_t k0 = grp - (grp % (64 / G)); k0 < n; k0 += ngrp) {   // wave-uniform trip count
@@ -1932,6 +2032,7 @@ __global__ void __launch_bounds__(256) hgx_nf_pull(const int32_t* __restrict__ l
                 n_newdeg += dg;
                 if (!becomes_full) n_newdeg_nf += dg;
             }
+            if (cpart) fuse_add_cs<W>(cplanes, sub, cones, nw);
         }
         if (sub == 0) {
             ++n_cand;
@@ -1950,6 +2051,10 @@ __global__ void __launch_bounds__(256) hgx_nf_pull(const int32_t* __restrict__ l
     wave_add_sh(ctr + cNewDeg, n_newdeg);
     wave_add_sh(ctr + cNewDegNF, n_newdeg_nf);
     wave_add_sh(ctr + cNfRows, n_rows);
+    if (cpart) {
+        fuse_flush<W>(cplanes, sub, cones);
+        fuse_store<W>(cplanes, &cdone, cpart);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2626,20 +2731,27 @@ __global__ void __launch_bounds__(256) hgx_count_reduce(int nslot, const int32_t
     constexpr int NR = kCountBlocks / kReduceSpan;
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= (int64_t)nslot * 1024 * NR) return;
-    const int r = (int)(i % NR);
-    const int64_t sj = i / NR;
+    // the source index varies fastest over the threads: a wave reads 64 consecutive words of a partial
+    // row (with the block range fastest its lanes read words kReduceSpan rows apart: 0.19 ms for config
+    // 2's three fused levels)
+    const int r = (int)(i / ((int64_t)nslot * 1024));   // < NR
+    const int64_t sj = i % ((int64_t)nslot * 1024);
     const int sl = (int)(sj / 1024), j = (int)(sj % 1024);
     const int wj = width[sl];
     if (j >= wj) return;
     const uint32_t* p = pp[sl] + j;
-    const int b0 = r * kReduceSpan, b1 = min(nblk[sl], b0 + kReduceSpan);
     u64 sum = (r == 0 && direct[sl]) ? direct[sl][j] : 0ull;   // a push level's counts from its finalise
-    for (int b = b0; b < b1; b += 8) {
-        uint32_t v[8];
+    // a slot of more than kCountBlocks blocks (the fused counts of a pull grid plus a hub grid): the
+    // thread takes every NR-th span
+    for (int b0 = r * kReduceSpan; b0 < nblk[sl]; b0 += NR * kReduceSpan) {
+        const int b1 = min(nblk[sl], b0 + kReduceSpan);
+        for (int b = b0; b < b1; b += 8) {
+            uint32_t v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = b + u < b1 ? p[(int64_t)(b + u) * wj] : 0u;
+            for (int u = 0; u < 8; ++u) v[u] = b + u < b1 ? p[(int64_t)(b + u) * wj] : 0u;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) sum += v[u];
+            for (int u = 0; u < 8; ++u) sum += v[u];
+        }
     }
     if (sum) atomicAdd(&counts[(int64_t)sl * 1024 + j], sum);
 }
@@ -3316,11 +3428,22 @@ struct BfsBatch {
     std::vector<u64*> fa;         // per level, A bits
     u64* pcnt = nullptr;          // [kDirectLevels][1024] per-source counts of push levels (whole graph)
     std::vector<char> direct;     // direct[d]: level d's counts are in pcnt (no counting pass)
-    // counting launched on g->stream2 as soon as a level is final, next to the following levels
-    // (cpart[d]: its block partials, cgrid blocks of W*64 words; null = counted at readout)
+    // Levels counted before the readout: cpart[d] = level d's block partials, cblk[d] blocks of W*64
+    // words (null = counted at readout).  Written by the kernels that stored the level's rows (fused
+    // counts, HGX_OPT_COUNT_FUSED) or by a counting pass launched on g->stream2 next to the following
+    // levels (HGX_COUNT_EAGER, A/B).
     std::vector<uint32_t*> cpart;
-    int cgrid = 0;
-    size_t cpart_bytes = 0;
+    std::vector<int32_t> cblk;
+    void set_cpart(size_t lev, uint32_t* p, int32_t blocks) {
+        if (cpart.size() <= lev) {
+            cpart.resize(lev + 1, nullptr);
+            cblk.resize(lev + 1, 0);
+        }
+        cpart[lev] = p;
+        cblk[lev] = blocks;
+    }
+    size_t cpart_bytes(size_t lev) const { return sizeof(uint32_t) * (size_t)cblk[lev] * W * 64; }
+    int32_t pass_levels = 0;      // levels the readout still has to count with a pass over their rows
 };
 
 struct hgx_bfs_result {
@@ -3989,14 +4112,25 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
     auto count_now = [&](size_t lev, hipEvent_t after) {   // level lev of bt: its counting pass on stream2
         if (!eager) return;
         if (lev < bt.direct.size() && bt.direct[lev]) return;
-        if (bt.cpart.size() <= lev) bt.cpart.resize(lev + 1, nullptr);
-        bt.cgrid = count_grid(A);
-        bt.cpart_bytes = sizeof(uint32_t) * (size_t)bt.cgrid * W * 64;
-        bt.cpart[lev] = (uint32_t*)g->alloc(bt.cpart_bytes);
+        if (lev < bt.cpart.size() && bt.cpart[lev]) return;   // counted by the kernels that wrote it
+        const int cgrid = count_grid(A);
+        bt.set_cpart(lev, nullptr, cgrid);
+        bt.cpart[lev] = (uint32_t*)g->alloc(bt.cpart_bytes(lev));
         HGX_HIP(hipStreamWaitEvent(g->stream2, after, 0));
-        hgx_count_rows<W><<<bt.cgrid, 256, 0, g->stream2>>>(A, bt.fa[lev], nullptr, bt.lvl[lev], bt.cpart[lev]);
+        hgx_count_rows<W><<<cgrid, 256, 0, g->stream2>>>(A, bt.fa[lev], nullptr, bt.lvl[lev], bt.cpart[lev]);
         HGX_CHECK_LAUNCH();
     };
+    // Fused level counts (HGX_OPT_COUNT_FUSED, whole-graph batches as for pcnt): the symmetric-mode
+    // kernels of rows of >= 8 words (more than 256 sources) that store a level's new rows (hgx_atom_pull2 + hgx_hub_finalize,
+    // hgx_nf_pull) count them into block partials; every other level kind is counted at readout.
+    // The LDS planes hold < 2^kFusePlanes rows per workgroup: a workgroup of the pull sees at most
+    // ceil(tiles / waves) * 256 rows, one of the hub finalise or the non-full pull at most
+    // ceil(atoms / groups) * (256 / G) -- about A / 4096 + 256 at the full grids, < 2^20 for any
+    // int32 atom count; fuse_rows_ok checks the actual grids.
+    auto fuse_rows_ok = [](int64_t items, int grid, int per_block) {
+        return ceil_div(items, (int64_t)grid * per_block) * per_block < ((int64_t)1 << kFusePlanes);
+    };
+    const bool fuse_ok = !tr && !g->shard && g->count_fused && MODE == kSym && Lay<W>::G >= 4;
     if (eager) {
         HGX_HIP(hipEventRecord(g->ev_count, s));
         count_now(0, g->ev_count);
@@ -4074,7 +4208,10 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         bool flag = false;    // counters in slot[0..cNum) once slot[cNum] == seq (mapped host memory)
         u64 seq = 0;
         u64* slot = nullptr;
+        uint32_t* cpart = nullptr;   // fused counts of the level's new rows: cblk block partials
+        int32_t cblk = 0;
     } pend[2];
+    auto cpart_size = [](int32_t blocks) { return sizeof(uint32_t) * (size_t)blocks * W * 64; };
     for (int k = 0; k < 2; ++k) {
         pend[k].h = h_sh + (size_t)k * kCtrBlock;
         pend[k].ev = g->pend_ev[k];
@@ -4131,10 +4268,12 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         if (h_new[cNewAtoms] == 0) {
             g->release(p.lvl_next, row_bytes);
             g->release(p.fa_next, bm_bytes);
+            if (p.cpart) g->release(p.cpart, cpart_size(p.cblk));
             return false;
         }
         bt.lvl.push_back(p.lvl_next);
         bt.fa.push_back(p.fa_next);
+        if (p.cpart) bt.set_cpart(bt.lvl.size() - 1, p.cpart, p.cblk);
         if (!p.flag) count_now(bt.lvl.size() - 1, p.ev);   // p.ev follows the level's kernels
         return true;
     };
@@ -4159,6 +4298,8 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         u64* lvl_next = (u64*)g->alloc(row_bytes);
         u64* fa_next = (u64*)g->alloc(bm_bytes);   // every word written by hgx_atom_pull
         u64* c = ctr + (size_t)d * kCtrBlock;
+        uint32_t* lv_cpart = nullptr;   // fused counts of this level's new rows (lv_cblk block partials)
+        int32_t lv_cblk = 0;
         const bool sparse = spec || (sparse_ok && push_volume < sparse_limit);
         int lflags = g->bfs_flags;
         if ((lflags & 16) && (int64_t)full_total * 16 < A) lflags &= ~4;   // adaptive full skip
@@ -4214,7 +4355,7 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                     tm.stop(e3);
                     Events e4 = tm.start(kKindHub, d);
                     hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis,
-                                                                   ever, full, lvl_next, fa_next, c, fm);
+                                                                   ever, full, lvl_next, fa_next, c, fm, nullptr);
                     HGX_CHECK_LAUNCH();
                     tm.stop(e4);
                 }
@@ -4237,9 +4378,14 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                 const u64* hasinc = (const u64*)g->hasinc;
                 hgx_nonfull_list<<<grid_for(ceil_div(A, 64), 256, 2048), 256, 0, s>>>(A, full, hasinc, clist, n_list);
                 HGX_CHECK_LAUNCH();
-                hgx_nf_pull<W><<<4096, 256, 0, s>>>(clist, n_list, g->inc_off, g->inc_row, g->inc_type, want_type,
-                                                    g->tgt_off, g->tgt_idx, fa, lvl, vis, ever, full, lvl_next, fa_next,
-                                                    c, fm, lflags);
+                constexpr int nf_grid = 4096;
+                if (fuse_ok && fuse_rows_ok(A, nf_grid, 256 / Lay<W>::G)) {
+                    lv_cblk = nf_grid;
+                    lv_cpart = (uint32_t*)g->alloc(cpart_size(lv_cblk));
+                }
+                hgx_nf_pull<W><<<nf_grid, 256, 0, s>>>(clist, n_list, g->inc_off, g->inc_row, g->inc_type, want_type,
+                                                       g->tgt_off, g->tgt_idx, fa, lvl, vis, ever, full, lvl_next,
+                                                       fa_next, c, fm, lflags, lv_cpart);
                 HGX_CHECK_LAUNCH();
                 tm.stop(e2);
             }
@@ -4394,12 +4540,22 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                 // a step against four (184 VGPRs, 2 waves/SIMD, dropped in r02); a tile's atoms placed in
                 // descending degree order (5.20 -> 5.13 ms, profiles/r02r_ab_pull_sort.log).  Bit 11 (A/B):
                 // half of a group's rows in flight at once (fewer VGPRs, more waves per SIMD).
+                // fused counts: the pull's blocks own the first pull_grid partial rows of the level, the hub
+                // finalise's blocks (when the snapshot has hubs) the hub_grid rows after them
+                const bool hubs = g->n_chunks > 0;
+                if (fuse_ok && fuse_rows_ok(ceil_div(A, 64) * 64, pull_grid, block) &&
+                    (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / Lay<W>::G))) {
+                    lv_cblk = pull_grid + (hubs ? hub_grid : 0);
+                    lv_cpart = (uint32_t*)g->alloc(cpart_size(lv_cblk));
+                }
                 if (lflags & 2048)
                     hgx_atom_pull2<W, 2, true, Lay<W>::G / 2><<<pull_grid, block, 0, s>>>(
-                        A, g->inc_off, g->inc_row, la, lf, vis, ever, full, lvl_next, fa_next, c, fm, lflags, own_bm);
+                        A, g->inc_off, g->inc_row, la, lf, vis, ever, full, lvl_next, fa_next, c, fm, lflags, own_bm,
+                        lv_cpart);
                 else
                     hgx_atom_pull2<W, 2, true, Lay<W>::G><<<pull_grid, block, 0, s>>>(
-                        A, g->inc_off, g->inc_row, la, lf, vis, ever, full, lvl_next, fa_next, c, fm, lflags, own_bm);
+                        A, g->inc_off, g->inc_row, la, lf, vis, ever, full, lvl_next, fa_next, c, fm, lflags, own_bm,
+                        lv_cpart);
             }
         }
         if (!(v2 && MODE == kSym))
@@ -4416,8 +4572,9 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
             HGX_CHECK_LAUNCH();
             tm.stop(e3);
             Events e4 = tm.start(kKindHub, d);
-            hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis, ever,
-                                                           full, lvl_next, fa_next, c, fm);
+            hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(
+                g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis, ever, full, lvl_next, fa_next, c, fm,
+                lv_cpart ? lv_cpart + (size_t)pull_grid * W * 64 : nullptr);
             HGX_CHECK_LAUNCH();
             tm.stop(e4);
         }
@@ -4445,6 +4602,8 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         pn.flag = flag_level;
         pn.seq = flag_seq;
         pn.slot = flag_slot;
+        pn.cpart = lv_cpart;
+        pn.cblk = lv_cblk;
         if (!flag_level) {
             tm.break_chain();
             HGX_HIP(hipMemcpyAsync(pn.h, c, sizeof(u64) * kCtrBlock, hipMemcpyDeviceToHost, s));
@@ -4471,6 +4630,7 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                     else wait_event(q.ev);
                     g->release(q.lvl_next, row_bytes);
                     g->release(q.fa_next, bm_bytes);
+                    if (q.cpart) g->release(q.cpart, cpart_size(q.cblk));
                 }
                 break;
             }
@@ -4480,6 +4640,12 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         res->stats.bytes_exchanged += ex->bytes_sent;
         res->stats.xwords_nonzero += ex->nz_words;
         res->stats.xwords_total += ex->words;
+    }
+    // levels left to a counting pass (level 0 of a whole-graph batch is {seed}: no pass, see ensure_counts)
+    for (size_t lev = (bt.pcnt && !g->shard) ? 1 : 0; lev < bt.lvl.size(); ++lev) {
+        const bool dir = lev < bt.direct.size() && bt.direct[lev];
+        const bool fused = !eager && lev < bt.cpart.size() && bt.cpart[lev];
+        if (!dir && !fused) ++bt.pass_levels;
     }
     g->release(vis, row_bytes);
     if (lf) g->release(lf, sizeof(u64) * (size_t)std::max<int64_t>(M, 1) * W);
@@ -4606,16 +4772,20 @@ void ensure_counts(hgx_bfs_result* r) {
         for (auto& bt : r->batches)
             for (size_t d = 0; d < bt.lvl.size(); ++d, ++k) {
                 const bool dir = d < bt.direct.size() && bt.direct[d];   // counted by the push finalise
-                const bool early = d < bt.cpart.size() && bt.cpart[d];   // counted next to the traversal
+                // counted by the kernels that wrote the level (fused) or next to the traversal (eager pass)
+                const bool early = d < bt.cpart.size() && bt.cpart[d];
+                // level 0 of a whole-graph batch is {seed}: count 1 each, set on the host below
+                const bool seed_level = d == 0 && bt.pcnt && !g->shard;
+                const bool pass = !dir && !early && !seed_level;
                 any_early |= early;
-                meta[k] = dir ? 0 : early ? bt.cgrid : grid;
+                meta[k] = early ? bt.cblk[d] : pass ? grid : 0;
                 meta[nslots + k] = bt.W * 64;
                 poff[k] = ptot;
-                fap[k] = (dir || early) ? nullptr : bt.fa[d];
+                fap[k] = pass ? bt.fa[d] : nullptr;
                 lvp[k] = bt.lvl[d];
                 dirp[k] = dir ? bt.pcnt + d * 1024 : nullptr;
                 early_p[k] = early ? bt.cpart[d] : nullptr;
-                if (!dir && !early) ptot += (int64_t)grid * bt.W * 64;
+                if (pass) ptot += (int64_t)grid * bt.W * 64;
             }
     }
     const size_t bytes = sizeof(u64) * 1024 * std::max<size_t>(nslots, 1);
@@ -4645,7 +4815,9 @@ void ensure_counts(hgx_bfs_result* r) {
     size_t k = 0;
     for (auto& bt : r->batches) {   // one launch per batch: blockIdx.y = its level slots
         const int nl = (int)bt.lvl.size();
-        if (nl > 0) {
+        bool any_pass = false;   // no launch when every level was counted by the kernels that wrote it
+        for (int d = 0; d < nl; ++d) any_pass |= fap[k + (size_t)d] != nullptr;
+        if (any_pass) {
             const dim3 gr((unsigned)grid, (unsigned)nl);
             const u64* const* fa_d = (const u64* const*)(dm + o_fap);
             const u64* const* lv_d = (const u64* const*)(dm + o_lvp);
@@ -4663,7 +4835,7 @@ void ensure_counts(hgx_bfs_result* r) {
         k += (size_t)nl;
     }
     HGX_HIP(hipMemsetAsync(dc, 0, bytes, g->stream));
-    if (any_early) {   // the passes already launched on stream2 come first
+    if (any_early && g->stream2) {   // the passes already launched on stream2 come first
         HGX_HIP(hipEventRecord(g->ev_count, g->stream2));
         HGX_HIP(hipStreamWaitEvent(g->stream, g->ev_count, 0));
     }
@@ -4681,15 +4853,19 @@ void ensure_counts(hgx_bfs_result* r) {
     g->release(dp, pbytes);
     g->release(dm, mbytes);
     for (auto& bt : r->batches) {   // stream2's passes were ordered before the synchronised reduce
-        for (auto& p : bt.cpart)
-            if (p) g->release(p, bt.cpart_bytes);
+        for (size_t d = 0; d < bt.cpart.size(); ++d)
+            if (bt.cpart[d]) g->release(bt.cpart[d], bt.cpart_bytes(d));
         bt.cpart.clear();
+        bt.cblk.clear();
     }
     k = 0;
     for (auto& bt : r->batches)
-        for (size_t d = 0; d < bt.lvl.size(); ++d, ++k)
+        for (size_t d = 0; d < bt.lvl.size(); ++d, ++k) {
+            const bool seed_level = d == 0 && bt.pcnt && !g->shard;   // V_0 = {seed}
             for (int s = 0; s < bt.S; ++s)
-                r->counts[(size_t)r->orig_of(bt.seed0 + s) * r->n_levels + d] = (int64_t)hc[k * 1024 + s];
+                r->counts[(size_t)r->orig_of(bt.seed0 + s) * r->n_levels + d] =
+                    seed_level ? 1 : (int64_t)hc[k * 1024 + s];
+        }
     for (auto& kv : r->isolated) r->counts[(size_t)kv.first * r->n_levels] += 1;
     r->counts_ready = true;
 }
@@ -4828,8 +5004,8 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
                 for (auto p : bt.lvl) r->g->release(p, r->row_bytes(bt));
                 for (auto p : bt.fa) r->g->release(p, r->bm_bytes());
                 if (bt.pcnt) r->g->release(bt.pcnt, sizeof(u64) * 1024 * kDirectLevels);
-                for (auto p : bt.cpart)
-                    if (p) r->g->release(p, bt.cpart_bytes);
+                for (size_t d = 0; d < bt.cpart.size(); ++d)
+                    if (bt.cpart[d]) r->g->release(bt.cpart[d], bt.cpart_bytes(d));
             }
             if (r->blk) block_release(r->g, *r->blk);
             r->g->refs.fetch_sub(1);   // the caller still holds its own reference
@@ -4994,6 +5170,7 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
             r->stats.launches[pull_kind] += 1;
             if (d < 64) r->stats.level_new[d] += (int64_t)c[cNewAtoms];
         }
+        r->stats.count_pass_levels += bt.pass_levels;
         r->batches.push_back(std::move(bt));
     }
     if (tm.on) HGX_HIP(hipEventRecord(tm.all.b, g->stream));
@@ -5195,8 +5372,8 @@ void hgx_bfs_result_free(hgx_bfs_result* r) {
             for (auto p : bt.lvl) g->release(p, r->row_bytes(bt));
             for (auto p : bt.fa) g->release(p, r->bm_bytes());
             if (bt.pcnt) g->release(bt.pcnt, sizeof(u64) * 1024 * kDirectLevels);
-            for (auto p : bt.cpart)
-                if (p) g->release(p, bt.cpart_bytes);
+            for (size_t d = 0; d < bt.cpart.size(); ++d)
+                if (bt.cpart[d]) g->release(bt.cpart[d], bt.cpart_bytes(d));
         }
         if (r->blk) block_release(g, *r->blk);
     }

@@ -154,6 +154,10 @@ typedef struct hgx_bfs_stats {
     /* multi-workgroup launches whose grid barrier timed out (their workgroups were not all resident
      * within the limit): the bitmaps were cleared and the seeds ran on the rows engine instead */
     int64_t coop_fallbacks;
+    /* levels of the rows engine (summed over batches) whose per-source counts the result readout still
+     * has to count with a pass over the level's rows: not counted by the kernels that wrote them
+     * (HGX_OPT_COUNT_FUSED, the frontier-push finalise) and not a whole-graph batch's seed level */
+    int64_t count_pass_levels;
 } hgx_bfs_stats;
 
 const char *hgx_version(void);
@@ -537,6 +541,13 @@ int  hgx_shard_graph_create(const hgx_shard *s, int32_t device, hgx_graph **out)
 #define HGX_OPT_SEQ_PACK_MIN 19
 #define HGX_OPT_XB_FLAT      20
 #define HGX_OPT_XB_STATIC    21
+/* (22 is HGX_OPT_SP_BUDGET, hgx_paths.h.)
+ * HGX_OPT_COUNT_FUSED (default 1): hgx_bfs_batch on a whole snapshot, symmetric generator, more than 256
+ * seeds in a batch (rows of >= 8 words): the dense-level kernels that store a level's new rows (hgx_atom_pull2 + hgx_hub_finalize,
+ * hgx_nf_pull) also count them per source, so hgx_bfs_result_counts needs no pass over those rows.
+ * 0 = every dense level is counted by the readout's pass (A/B; the results are the same).
+ * hgx_bfs_stats.count_pass_levels tells how many levels of a call were left to the pass. */
+#define HGX_OPT_COUNT_FUSED  23
 /* Coalescing statistics of a graph since its creation: device batches run by the packed pattern path
  * and caller batches they served (caller / device = the mean coalescing factor). */
 int  hgx_query_coalesce_stats(hgx_graph *g, int64_t *device_batches, int64_t *caller_batches);
