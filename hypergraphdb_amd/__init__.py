@@ -6,13 +6,15 @@ This package is the host-side mirror of the reference interfaces on that path:
   algorithms                    DefaultALGenerator / HGBreadthFirstTraversal / bfs_batch
   query                         hg.and/or/type/incident/orderedLink, GpuAndToQuery, GpuOrToQuery, pattern_batch,
                                 pattern_batch_dnf (include/hgx_dnf.h)
-  classics                      GraphClassics.dijkstra / shortest_paths (include/hgx_paths.h)
+  classics                      GraphClassics.dijkstra / shortest_paths (include/hgx_paths.h);
+                                hop_paths -> HopPaths, BfsResult.paths / depths / predecessors: unit-weight
+                                shortest paths read out of a batched BFS (include/hgx_hops.h)
 """
 from ._lib import HGXError, HGXUnsupported, lib  # noqa: F401
 from .algorithms import (AtomTypeCondition, BfsResult, DefaultALGenerator, HGBreadthFirstTraversal,  # noqa: F401
-                         SequenceResult, bfs_sequence,
+                         HopPaths, SequenceResult, bfs_sequence,
                          HGException, bfs_batch)
-from .classics import GraphClassics, LinkWeights, ShortestPathsResult, shortest_paths  # noqa: F401
+from .classics import GraphClassics, LinkWeights, ShortestPathsResult, hop_paths, shortest_paths  # noqa: F401
 from .query import (And, ArityCondition, GpuAndToQuery, GpuOrToQuery, HGQueryConfiguration, LinkCondition,  # noqa: F401
                     Or, PositionedIncidentCondition, TypePlusCondition, find_all, hg, pattern_batch,
                     pattern_batch_dnf, to_dnf)

@@ -86,6 +86,12 @@ EXPORTED_PATHS = (
 # Every symbol include/hgx_dnf.h declares (checked by tests/test_dnf_ref.py without a GPU).
 EXPORTED_DNF = ("hgx_pattern_batch_dnf", "hgx_query_result_union_stats")
 
+# Every symbol include/hgx_hops.h declares (checked by tests/test_hop_ref.py without a GPU).
+EXPORTED_HOPS = (
+    "hgx_bfs_result_paths", "hgx_hop_paths_info", "hgx_hop_paths_offsets", "hgx_hop_paths_read", "hgx_hop_paths_stats",
+    "hgx_hop_paths_free", "hgx_bfs_result_depth_row", "hgx_bfs_result_predecessor_row",
+)
+
 
 class GraphDesc(C.Structure):
     _fields_ = [("num_atoms", C.c_int64), ("num_links", C.c_int64), ("link_atom", C.c_void_p),
@@ -254,6 +260,16 @@ def lib():
         "hgx_pattern_batch_dnf": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)], C.c_int),
         "hgx_query_result_union_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)], C.c_int),
+        # include/hgx_hops.h
+        "hgx_bfs_result_paths": ([vp, vp, vp, i32, C.POINTER(vp)], C.c_int),
+        "hgx_hop_paths_info": ([vp, C.POINTER(i32), C.POINTER(i64)], C.c_int),
+        "hgx_hop_paths_offsets": ([vp, vp, vp], C.c_int),
+        "hgx_hop_paths_read": ([vp, vp, vp], C.c_int),
+        "hgx_hop_paths_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double)], C.c_int),
+        "hgx_hop_paths_free": ([vp], None),
+        "hgx_bfs_result_depth_row": ([vp, i32, i64, i64, vp], C.c_int),
+        "hgx_bfs_result_predecessor_row": ([vp, i32, i64, i64, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)

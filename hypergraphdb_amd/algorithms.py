@@ -109,6 +109,40 @@ class BfsResult:
         check(lib().hgx_bfs_result_depth_of(self._h, int(seed_index), int(atom), C.byref(d)))
         return d.value
 
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("result closed")
+        return self._h
+
+    def paths(self, seed_indices, goals) -> "HopPaths":
+        """The shortest hop path from seed ``seed_indices[i]`` to ``goals[i]`` for every i (hgx_hops.h):
+        what GraphClassics.dijkstra(seed, goal, generator) finds with the default weight, rule R
+        predecessors.  The generator is the one this result was made with."""
+        si = np.ascontiguousarray(seed_indices, np.int32)
+        go = np.ascontiguousarray(goals, np.int32)
+        if si.shape != go.shape or si.ndim != 1:
+            raise ValueError("seed_indices and goals: two 1-d sequences of one length")
+        h = C.c_void_p()
+        check(lib().hgx_bfs_result_paths(self.handle, ptr(si), ptr(go), len(si), C.byref(h)))
+        return HopPaths(h, self.seeds[si] if len(si) else np.zeros(0, np.int32), go, owner=self)
+
+    def depths(self, seed_index: int, first: int = 0, n: int | None = None) -> np.ndarray:
+        """The distanceMatrix row of one seed over atoms [first, first + n): -1 = not reached."""
+        n = self.snapshot.A - first if n is None else n
+        out = np.empty(max(n, 1), np.int32)
+        check(lib().hgx_bfs_result_depth_row(self.handle, int(seed_index), int(first), int(n), ptr(out)))
+        return out[:n]
+
+    def predecessors(self, seed_index: int, first: int = 0, n: int | None = None):
+        """(predecessor atoms, their links) of one seed over atoms [first, first + n): -1 for the seed
+        and for atoms not reached (the predecessorMatrix row, rule R)."""
+        n = self.snapshot.A - first if n is None else n
+        pa = np.empty(max(n, 1), np.int32)
+        pl = np.empty(max(n, 1), np.int32)
+        check(lib().hgx_bfs_result_predecessor_row(self.handle, int(seed_index), int(first), int(n), ptr(pa), ptr(pl)))
+        return pa[:n], pl[:n]
+
     def stats(self, accounting=True, raw=False):
         """Kernel timings (timing enabled), algorithmic bytes; with ``accounting`` also the
         TEPS numerator, |U_d| and the SURVEY.md 8(d) bytes (runs the accounting kernels).
@@ -121,6 +155,75 @@ class BfsResult:
         if self._h is not None:
             lib().hgx_bfs_result_free(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HopPaths:
+    """Shortest hop paths of a batch of (seed, goal) pairs (hgx_hop_paths, host resident).
+    ``hops[i]``: links on pair i's path (-1: not reached); ``reached``; ``path(i)``."""
+
+    def __init__(self, handle, starts, goals, owner=None):
+        self._h = handle
+        self.starts, self.goals = starts, goals
+        self.owner = owner          # the BfsResult the paths were read from
+        self.owns_result = False    # hop_paths: the BfsResult was made for this object and closes with it
+        n, tot = C.c_int32(), C.c_int64()
+        check(lib().hgx_hop_paths_info(handle, C.byref(n), C.byref(tot)))
+        self.n_pairs, self.total_atoms = n.value, tot.value
+        self.offsets = np.zeros(self.n_pairs + 1, np.int64)
+        self.hops = np.zeros(self.n_pairs, np.int32)
+        check(lib().hgx_hop_paths_offsets(handle, ptr(self.offsets), ptr(self.hops)))
+        self.reached = self.hops >= 0
+        self._link_off = self.offsets[:-1] - np.concatenate(([0], np.cumsum(self.reached)[:-1])) if self.n_pairs else \
+            np.zeros(0, np.int64)
+        self._atoms = self._links = None
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("result closed")
+        return self._h
+
+    def _read(self):
+        if self._atoms is None:
+            atoms = np.empty(max(self.total_atoms, 1), np.int32)
+            links = np.empty(max(self.total_atoms, 1), np.int32)
+            check(lib().hgx_hop_paths_read(self.handle, ptr(atoms), ptr(links)))
+            self._atoms, self._links = atoms, links
+
+    def path(self, i: int):
+        """(atoms, links) of pair ``i``: atoms = start .. goal, links[k] joins atoms[k] and atoms[k + 1];
+        two empty arrays when the goal was not reached."""
+        self._read()
+        h = int(self.hops[i])
+        if h < 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+        o, lo = int(self.offsets[i]), int(self._link_off[i])
+        return self._atoms[o:o + h + 1], self._links[lo:lo + h]
+
+    def stats(self) -> dict:
+        s, e, p = C.c_int64(), C.c_int64(), C.c_int64()
+        ms, by = C.c_double(), C.c_double()
+        check(lib().hgx_hop_paths_stats(self.handle, C.byref(s), C.byref(e), C.byref(p), C.byref(ms), C.byref(by)))
+        return {"steps": s.value, "entries": e.value, "probes": p.value, "ms_total": ms.value, "bytes": by.value}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().hgx_hop_paths_free(self._h)
+            self._h = None
+            if self.owns_result and self.owner is not None:
+                self.owner.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

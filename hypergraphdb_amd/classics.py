@@ -6,6 +6,10 @@ Reference (C = core/src/java/org/hypergraphdb):
 
 ``shortest_paths`` is the batched entry (many (start, goal) pairs per call) the GPU engine is built
 for; ``GraphClassics.dijkstra`` keeps the reference's single-pair signature on top of a batch of one.
+``hop_paths`` is the batched unit-weight form (the reference's 3-argument dijkstra, GraphClassics.java:80-83):
+one batched BFS over the distinct starts and the backtrace of include/hgx_hops.h.  It is the faster way from a
+few tens of pairs a call; a single pair is faster on the relaxation engine, so ``GraphClassics.dijkstra``
+stays there.
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .algorithms import DefaultALGenerator
+from .algorithms import DefaultALGenerator, HopPaths, bfs_batch
 
 NO_GOAL = _lib.HGX_NO_GOAL
 
@@ -164,6 +168,26 @@ def shortest_paths(snapshot, starts, goals, generator: DefaultALGenerator | None
         if own is not None:
             own.close()
     return ShortestPathsResult(snapshot, h, s, g)
+
+
+def hop_paths(snapshot, starts, goals, generator: DefaultALGenerator | None = None, max_depth=None) -> HopPaths:
+    """GraphClassics.dijkstra(starts[i], goals[i], generator) with the default weight (1.0 per link,
+    C/algorithms/GraphClassics.java:80-83) for every i: one batched BFS over the distinct starts and the
+    backtrace of include/hgx_hops.h over its level rows.  ``max_depth`` bounds the BFS: goals beyond it
+    are reported as not reached.  The returned HopPaths keeps the BfsResult alive (``.owner``)."""
+    s = np.ascontiguousarray(starts, np.int32)
+    g = np.ascontiguousarray(goals, np.int32)
+    if s.shape != g.shape or s.ndim != 1:
+        raise ValueError("starts and goals: two 1-d sequences of one length")
+    distinct, index = np.unique(s, return_inverse=True)
+    res = bfs_batch(snapshot, distinct, max_depth, generator)
+    try:
+        hp = res.paths(index.astype(np.int32), g)
+    except Exception:
+        res.close()
+        raise
+    hp.owns_result = True
+    return hp
 
 
 class GraphClassics:

@@ -3421,49 +3421,6 @@ struct ZeroList {
     }
 };
 
-struct BfsBatch {
-    int32_t seed0 = 0, S = 0, W = 0;
-    int32_t n_expanded = 0;       // levels whose frontier was expanded (advance() iterated)
-    std::vector<u64*> lvl;        // per level, A*W words (rows valid where fa bit set)
-    std::vector<u64*> fa;         // per level, A bits
-    u64* pcnt = nullptr;          // [kDirectLevels][1024] per-source counts of push levels (whole graph)
-    std::vector<char> direct;     // direct[d]: level d's counts are in pcnt (no counting pass)
-    // Levels counted before the readout: cpart[d] = level d's block partials, cblk[d] blocks of W*64
-    // words (null = counted at readout).  Written by the kernels that stored the level's rows (fused
-    // counts, HGX_OPT_COUNT_FUSED) or by a counting pass launched on g->stream2 next to the following
-    // levels (HGX_COUNT_EAGER, A/B).
-    std::vector<uint32_t*> cpart;
-    std::vector<int32_t> cblk;
-    void set_cpart(size_t lev, uint32_t* p, int32_t blocks) {
-        if (cpart.size() <= lev) {
-            cpart.resize(lev + 1, nullptr);
-            cblk.resize(lev + 1, 0);
-        }
-        cpart[lev] = p;
-        cblk[lev] = blocks;
-    }
-    size_t cpart_bytes(size_t lev) const { return sizeof(uint32_t) * (size_t)cblk[lev] * W * 64; }
-    int32_t pass_levels = 0;      // levels the readout still has to count with a pass over their rows
-};
-
-struct hgx_bfs_result {
-    hgx_graph* g = nullptr;
-    int32_t n_seeds = 0, n_levels = 0;
-    std::vector<BfsBatch> batches;
-    hgx_bfs_stats stats{};
-    bool counts_ready = false, accounting_ready = false;
-    bool typed = false;
-    std::map<int32_t, int32_t> isolated;   // shards: seed index -> owned seed atom without incidence
-    std::vector<int64_t> counts;   // [n_seeds * n_levels]
-    // Seeds finished by the workgroup engine (HGX_OPT_BFS_BLOCK); the batches then hold only the
-    // others, compacted: orig[k] = seed index of batch seed k, compact[i] = k (-1: a workgroup seed).
-    std::unique_ptr<hgx::BlockSet> blk;
-    std::vector<int32_t> orig, compact;
-    int32_t orig_of(int32_t k) const { return orig.empty() ? k : orig[k]; }
-    size_t row_bytes(const BfsBatch& b) const { return sizeof(u64) * (size_t)g->A * b.W; }
-    size_t bm_bytes() const { return sizeof(u64) * (size_t)(g->A / 64 + 2); }
-};
-
 namespace {
 
 struct Events {
@@ -5016,6 +4973,7 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
     g->refs.fetch_add(1);
     r->n_seeds = n_seeds;
     r->typed = o.link_type >= 0;
+    r->opts = o;
 
     Timer tm(g);
     if (tm.on) HGX_HIP(hipEventRecord(tm.all.a, g->stream));
@@ -5376,6 +5334,8 @@ void hgx_bfs_result_free(hgx_bfs_result* r) {
                 if (bt.cpart[d]) g->release(bt.cpart[d], bt.cpart_bytes(d));
         }
         if (r->blk) block_release(g, *r->blk);
+        if (r->hop_depth) g->release(r->hop_depth, sizeof(int32_t) * (size_t)std::max<int64_t>(g->A, 1));
+        if (r->hop_key) g->release(r->hop_key, sizeof(u64) * (size_t)std::max<int64_t>(g->A, 1));
     }
     delete r;
     if (g) graph_release(g);

@@ -19,14 +19,19 @@
 #include <condition_variable>
 #include <cstdint>
 #include <deque>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/hgx_dnf.h"
+#include "../../include/hgx_hops.h"
 #include "../../include/hgx_paths.h"
 
 namespace hgx {
+
+typedef unsigned long long u64;
 
 // Engine knobs.  The product library reads no tuning setting from the environment (a library loaded into
 // a JVM must not change behaviour with whichever call read the environment first, and getenv racing a
@@ -460,3 +465,55 @@ size_t union_temp_bytes(int64_t cap, hipStream_t s);
 // Enqueues the union on s: no synchronisation, nothing read back by the host.
 void union_launch(const UnionArgs& a, hipStream_t s);
 }  // namespace hgx
+
+// One batch (<= 1024 seeds) of a batched BFS and the result object of hgx_bfs_batch (hgx_bfs.hip makes and
+// frees them; hgx_hops.hip reads the level rows).
+struct BfsBatch {
+    int32_t seed0 = 0, S = 0, W = 0;
+    int32_t n_expanded = 0;       // levels whose frontier was expanded (advance() iterated)
+    std::vector<hgx::u64*> lvl;   // per level, A*W words (rows valid where fa bit set)
+    std::vector<hgx::u64*> fa;    // per level, A bits
+    hgx::u64* pcnt = nullptr;     // [kDirectLevels][1024] per-source counts of push levels (whole graph)
+    std::vector<char> direct;     // direct[d]: level d's counts are in pcnt (no counting pass)
+    // Levels counted before the readout: cpart[d] = level d's block partials, cblk[d] blocks of W*64
+    // words (null = counted at readout).  Written by the kernels that stored the level's rows (fused
+    // counts, HGX_OPT_COUNT_FUSED) or by a counting pass launched on g->stream2 next to the following
+    // levels (HGX_COUNT_EAGER, A/B).
+    std::vector<uint32_t*> cpart;
+    std::vector<int32_t> cblk;
+    void set_cpart(size_t lev, uint32_t* p, int32_t blocks) {
+        if (cpart.size() <= lev) {
+            cpart.resize(lev + 1, nullptr);
+            cblk.resize(lev + 1, 0);
+        }
+        cpart[lev] = p;
+        cblk[lev] = blocks;
+    }
+    size_t cpart_bytes(size_t lev) const { return sizeof(uint32_t) * (size_t)cblk[lev] * W * 64; }
+    int32_t pass_levels = 0;      // levels the readout still has to count with a pass over their rows
+};
+
+struct hgx_bfs_result {
+    hgx_graph* g = nullptr;
+    int32_t n_seeds = 0, n_levels = 0;
+    std::vector<BfsBatch> batches;
+    hgx_bfs_stats stats{};
+    bool counts_ready = false, accounting_ready = false;
+    bool typed = false;
+    hgx_algen_opts opts{HGX_NO_TYPE, 1, 1, 0, 0};   // the generator the result was made with (hgx_hops.h readers)
+    std::map<int32_t, int32_t> isolated;   // shards: seed index -> owned seed atom without incidence
+    std::vector<int64_t> counts;   // [n_seeds * n_levels]
+    // Seeds finished by the workgroup engine (HGX_OPT_BFS_BLOCK); the batches then hold only the
+    // others, compacted: orig[k] = seed index of batch seed k, compact[i] = k (-1: a workgroup seed).
+    std::unique_ptr<hgx::BlockSet> blk;
+    std::vector<int32_t> orig, compact;
+    // hgx_hops.h row readers: the depth and predecessor-key rows of one seed, kept until the result is freed
+    // (12 A bytes of pool memory; hop_seed = the seed index they belong to, hop_have_key = the key row is filled).
+    int32_t hop_seed = -1;
+    bool hop_have_key = false;
+    int32_t* hop_depth = nullptr;   // [A]
+    hgx::u64* hop_key = nullptr;    // [A] (predecessor atom << 32) | link atom
+    int32_t orig_of(int32_t k) const { return orig.empty() ? k : orig[k]; }
+    size_t row_bytes(const BfsBatch& b) const { return sizeof(hgx::u64) * (size_t)g->A * b.W; }
+    size_t bm_bytes() const { return sizeof(hgx::u64) * (size_t)(g->A / 64 + 2); }
+};
