@@ -56,6 +56,7 @@ HGX_OPT_XB_FLAT = 20
 HGX_OPT_XB_STATIC = 21
 HGX_OPT_SP_BUDGET = 22   # include/hgx_paths.h
 HGX_OPT_COUNT_FUSED = 23
+HGX_OPT_NF_PULL = 24
 HGX_NO_GOAL = -1
 
 # Every symbol include/hgx.h declares (checked by tests/test_abi.py without a GPU).

@@ -1923,6 +1923,81 @@ __global__ void __launch_bounds__(256) hgx_nonfull_list(int64_t A, const u64* __
     }
 }
 
+// The entries [b, e) of one atom's incidence for a G-lane group: acc |= the frontier rows of the entries'
+// targets, G entries a step, leaving once acc | old covers FULL (early).  Shared by hgx_nf_pull and the hub
+// chunks of hgx_nf_pull_heavy; b, e and every branch around a shuffle are group-uniform.
+template <int W>
+__device__ __forceinline__ void nf_range(int64_t b, int64_t e, const int32_t* __restrict__ inc_row,
+                                         const int32_t* __restrict__ inc_type, int32_t want_type,
+                                         const int64_t* __restrict__ tgt_off, const int32_t* __restrict__ tgt_idx,
+                                         const u64* __restrict__ fa, const u64* __restrict__ lvl,
+                                         typename Vec<Lay<W>::WPL>::T FULL, typename Vec<Lay<W>::WPL>::T old,
+                                         typename Vec<Lay<W>::WPL>::T& acc, bool early, u64& n_ent, u64& n_pins,
+                                         u64& n_rows) {
+    constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G;
+    typedef Vec<WPL> V;
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1), base = lane & ~(G - 1);
+    const u64 gmask = (1ull << G) - 1ull;
+    for (int64_t i0 = b; i0 < e; i0 += G) {   // group-uniform
+        const int64_t q = i0 + sub;
+        int32_t myL = q < e ? inc_row[q] : -1;
+        if (myL >= 0 && want_type >= 0 && inc_type[q] != want_type) myL = -1;
+        int64_t bme = 0;
+        int nme = 0;
+        if (myL >= 0) {
+            bme = tgt_off[myL];
+            nme = (int)(tgt_off[myL + 1] - bme);
+            ++n_ent;
+            n_pins += (u64)nme;
+        }
+        int32_t v[G];
+        int nn[G];
+        int64_t bb[G];
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            bb[j] = __shfl(bme, base + j);
+            nn[j] = __shfl(nme, base + j);
+            v[j] = sub < nn[j] ? tgt_idx[bb[j] + sub] : -1;
+        }
+        unsigned pa = 0;
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+            if (v[j] >= 0 && bit(fa, v[j])) pa |= 1u << j;
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const unsigned ga = (unsigned)((__ballot((pa >> j) & 1u) >> base) & gmask);
+            if (ga) {   // group-uniform
+                typename V::T r[G];
+#pragma unroll
+                for (int kk = 0; kk < G; ++kk) {
+                    const int32_t vk = __shfl(v[j], base + kk);
+                    r[kk] = ((ga >> kk) & 1u) ? V::ld(lvl + (int64_t)vk * W + sub * WPL) : V::zero();
+                }
+#pragma unroll
+                for (int kk = 0; kk < G; ++kk) acc |= r[kk];
+                n_rows += __popc(ga);
+            }
+            if (nn[j] > G) {   // a link longer than G (rare): the rest of its targets
+                for (int64_t p = bb[j] + G; p < bb[j] + nn[j]; p += G) {
+                    const int64_t qq = p + sub;
+                    const int32_t myv = qq < bb[j] + nn[j] ? tgt_idx[qq] : -1;
+                    const unsigned g2 = (unsigned)((__ballot(myv >= 0 && bit(fa, myv)) >> base) & gmask);
+                    typename V::T r[G];
+#pragma unroll
+                    for (int kk = 0; kk < G; ++kk) {
+                        const int32_t vk = __shfl(myv, base + kk);
+                        r[kk] = ((g2 >> kk) & 1u) ? V::ld(lvl + (int64_t)vk * W + sub * WPL) : V::zero();
+                    }
+#pragma unroll
+                    for (int kk = 0; kk < G; ++kk) acc |= r[kk];
+                    n_rows += __popc(g2);
+                }
+            }
+        }
+        if (early && i0 + G < e && group_all<G>(V::eq(acc | old, FULL))) break;
+    }
+}
+
 template <int W>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) hgx_nf_pull(const int32_t* __restrict__ list, const u64* __restrict__ n_list,
                                                    const int64_t* __restrict__ inc_off,
@@ -1942,8 +2017,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
     if (cpart) fuse_zero<W>(cplanes, &cdone);
     const bool early = flags & 2;
-    const int lane = threadIdx.x & 63, sub = lane & (G - 1), base = lane & ~(G - 1);
-    const u64 gmask = (1ull << G) - 1ull;
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1);
     const int64_t grp = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
     const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) / G;
     const typename V::T FULL = full_part<W>(fm, sub);
@@ -1959,64 +2033,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
         const bool ev = bit(ever, t);
         const typename V::T old = ev ? V::ld(vis + t * W + sub * WPL) : V::zero();
         typename V::T acc = V::zero();
-        for (int64_t i0 = b; i0 < e; i0 += G) {   // group-uniform
-            const int64_t q = i0 + sub;
-            int32_t myL = q < e ? inc_row[q] : -1;
-            if (myL >= 0 && want_type >= 0 && inc_type[q] != want_type) myL = -1;
-            int64_t bme = 0;
-            int nme = 0;
-            if (myL >= 0) {
-                bme = tgt_off[myL];
-                nme = (int)(tgt_off[myL + 1] - bme);
-                ++n_ent;
-                n_pins += (u64)nme;
-            }
-            int32_t v[G];
-            int nn[G];
-            int64_t bb[G];
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                bb[j] = __shfl(bme, base + j);
-                nn[j] = __shfl(nme, base + j);
-                v[j] = sub < nn[j] ? tgt_idx[bb[j] + sub] : -1;
-            }
-            unsigned pa = 0;
-#pragma unroll
-            for (int j = 0; j < G; ++j)
-                if (v[j] >= 0 && bit(fa, v[j])) pa |= 1u << j;
-#pragma unroll
-            for (int j = 0; j < G; ++j) {
-                const unsigned ga = (unsigned)((__ballot((pa >> j) & 1u) >> base) & gmask);
-                if (ga) {   // group-uniform
-                    typename V::T r[G];
-#pragma unroll
-                    for (int kk = 0; kk < G; ++kk) {
-                        const int32_t vk = __shfl(v[j], base + kk);
-                        r[kk] = ((ga >> kk) & 1u) ? V::ld(lvl + (int64_t)vk * W + sub * WPL) : V::zero();
-                    }
-#pragma unroll
-                    for (int kk = 0; kk < G; ++kk) acc |= r[kk];
-                    n_rows += __popc(ga);
-                }
-                if (nn[j] > G) {   // a link longer than G (rare): the rest of its targets
-                    for (int64_t p = bb[j] + G; p < bb[j] + nn[j]; p += G) {
-                        const int64_t qq = p + sub;
-                        const int32_t myv = qq < bb[j] + nn[j] ? tgt_idx[qq] : -1;
-                        const unsigned g2 = (unsigned)((__ballot(myv >= 0 && bit(fa, myv)) >> base) & gmask);
-                        typename V::T r[G];
-#pragma unroll
-                        for (int kk = 0; kk < G; ++kk) {
-                            const int32_t vk = __shfl(myv, base + kk);
-                            r[kk] = ((g2 >> kk) & 1u) ? V::ld(lvl + (int64_t)vk * W + sub * WPL) : V::zero();
-                        }
-#pragma unroll
-                        for (int kk = 0; kk < G; ++kk) acc |= r[kk];
-                        n_rows += __popc(g2);
-                    }
-                }
-            }
-            if (early && i0 + G < e && group_all<G>(V::eq(acc | old, FULL))) break;
-        }
+        nf_range<W>(b, e, inc_row, inc_type, want_type, tgt_off, tgt_idx, fa, lvl, FULL, old, acc, early, n_ent, n_pins,
+                    n_rows);
         const typename V::T nw = acc & ~old;
         if (group_any<G>(V::nz(nw))) {
             V::st(lvl_next + t * W + sub * WPL, nw);
@@ -2055,6 +2073,280 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
         fuse_flush<W>(cplanes, sub, cones);
         fuse_store<W>(cplanes, &cdone, cpart);
     }
+}
+
+// hgx_nf_pull with the cover test every E entries (E < G; HGX_OPT_NF_PULL).  The listed atoms of config 2's
+// late levels cover after one to three links, so the G-entry step above loads CSR lines and frontier rows
+// past the point where the atom's row is decided.  Here a group keeps its G entry slots busy with G / E
+// atoms of E entries each: lane `sub` loads entry sub % E of atom slot sub / E, the targets of the G links
+// are read as above, and the frontier rows go out one per entry slot and round (G row loads in flight),
+// each into its atom's accumulator.  After the step every atom slot tests acc | old == FULL; a slot whose
+// atom covered or ran out of entries writes the atom's row and takes the group's next listed atom (group
+// g owns list positions g, g + ngrp, ...).  The row of a target equal to t is not loaded (it is a subset
+// of vis[t]).  Every __shfl / __ballot below reads lanes of the calling lane's own group, and every
+// branch or loop around one is group-uniform.  The scalar state of atom slot a (t, pos, end, deg, ev,
+// live) lives in the E lanes of the slot, the row parts acc[a] / old[a] in every lane.
+template <int W, int E, int NS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) hgx_nf_pull_e(const int32_t* __restrict__ list, const u64* __restrict__ n_list,
+                                                   const int64_t* __restrict__ inc_off,
+                                                   const int32_t* __restrict__ inc_row,
+                                                   const int32_t* __restrict__ inc_type, int32_t want_type,
+                                                   const int64_t* __restrict__ tgt_off,
+                                                   const int32_t* __restrict__ tgt_idx, const u64* __restrict__ fa,
+                                                   const u64* __restrict__ lvl, u64* __restrict__ vis,
+                                                   u64* __restrict__ ever, u64* __restrict__ full,
+                                                   u64* __restrict__ lvl_next, u64* __restrict__ fa_next,
+                                                   u64* __restrict__ ctr, FullMask fm, int flags,
+                                                   uint32_t* __restrict__ cpart, u64* __restrict__ resid) {
+    constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G, NA = NS / E;   // NS <= G entry slots (lanes sub < NS)
+    static_assert(G >= 4 && G <= 8 && E >= 1 && E < G && NS <= G && NS % E == 0, "nf pull: E divides NS <= G <= 8 (byte masks)");
+    typedef Vec<WPL> V;
+    __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
+    __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
+    if (cpart) fuse_zero<W>(cplanes, &cdone);
+    const bool early = flags & 2;
+    const int lane = threadIdx.x & 63, sub = lane & (G - 1), base = lane & ~(G - 1);
+    const int my_a = sub / E, my_e = sub % E;
+    const u64 gmask = (1ull << G) - 1ull;
+    const int64_t grp = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
+    const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) / G;
+    const typename V::T FULL = full_part<W>(fm, sub);
+    const int64_t n = (int64_t)*n_list;
+    typename V::T cones = V::zero();   // fused counts: the lane's carry-save level
+    u64 n_ent = 0, n_pins = 0, n_rows = 0, n_newdeg = 0, n_newdeg_nf = 0;
+    uint32_t n_cand = 0, n_vis = 0, n_new = 0, n_full = 0;   // a group sees < 2^31 listed atoms
+    int32_t t = 0;
+    int64_t pos = 0, end = 0, deg = 0;
+    bool ev = false, live = false;
+    typename V::T acc[NA];   // vis[t] | the frontier rows so far (vis[t] is read again for the new bits)
+#pragma unroll
+    for (int a = 0; a < NA; ++a) acc[a] = V::zero();
+    int64_t cursor = grp;   // the group's next list position
+    for (;;) {              // trip count group-uniform (the state below is the same in every lane of a group)
+        // empty atom slots take the next listed atoms
+        unsigned em = 0;
+        {
+            const unsigned el = (unsigned)((__ballot(!live) >> base) & gmask);
+#pragma unroll
+            for (int a = 0; a < NA; ++a) em |= ((el >> (a * E)) & 1u) << a;
+        }
+        if (em && cursor < n) {   // group-uniform
+            const int64_t k = cursor + (int64_t)__popc(em & ((1u << my_a) - 1u)) * ngrp;
+            const bool got = sub < NS && !live && k < n;
+            if (got) {
+                t = list[k];
+                pos = inc_off[t];
+                end = inc_off[t + 1];
+                deg = end - pos;
+                if (resid && deg > kHeavyDegree) end = pos + kHeavyDegree;   // a hub: its first entries here
+                ev = bit(ever, t);
+                live = true;
+            }
+            cursor += (int64_t)__popc(em) * ngrp;
+            const unsigned gl = (unsigned)((__ballot(got) >> base) & gmask);
+            const unsigned evl = (unsigned)((__ballot(ev) >> base) & gmask);
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+                if ((gl >> (a * E)) & 1u) {   // group-uniform
+                    const int64_t ta = __shfl(t, base + a * E);
+                    acc[a] = ((evl >> (a * E)) & 1u) ? V::ld(vis + ta * W + sub * WPL) : V::zero();
+                }
+        }
+        if (!group_any<G>(live)) break;   // no atom in flight and none left in the list
+        // one step: E entries of every live atom
+        const int64_t q = pos + my_e;
+        int32_t myL = live && q < end ? inc_row[q] : -1;
+        if (myL >= 0 && want_type >= 0 && inc_type[q] != want_type) myL = -1;
+        int64_t bme = 0;
+        int nme = 0;
+        if (myL >= 0) {
+            bme = tgt_off[myL];
+            nme = (int)(tgt_off[myL + 1] - bme);
+            ++n_ent;
+            n_pins += (u64)nme;
+        }
+        int32_t v[NS];
+        u64 gam = 0;   // byte j: the lanes whose target of slot j's link is on the frontier
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const int64_t bj = __shfl(bme, base + j);
+            const int nj = __shfl(nme, base + j);
+            const int32_t tj = __shfl(t, base + j);   // nj == 0 where slot j has no entry
+            v[j] = sub < nj ? tgt_idx[bj + sub] : -1;
+            if (v[j] == tj) v[j] = -1;
+            if (nj > G) {   // a link longer than G (rare; group-uniform): the rest of its targets
+                for (int64_t p = bj + G; p < bj + nj; p += G) {
+                    const int64_t qq = p + sub;
+                    int32_t myv = qq < bj + nj ? tgt_idx[qq] : -1;
+                    if (myv == tj) myv = -1;
+                    const unsigned g2 = (unsigned)((__ballot(myv >= 0 && bit(fa, myv)) >> base) & gmask);
+                    typename V::T r[G];
+#pragma unroll
+                    for (int kk = 0; kk < G; ++kk) {
+                        const int32_t vk = __shfl(myv, base + kk);
+                        r[kk] = ((g2 >> kk) & 1u) ? V::ld(lvl + (int64_t)vk * W + sub * WPL) : V::zero();
+                    }
+#pragma unroll
+                    for (int kk = 0; kk < G; ++kk) acc[j / E] |= r[kk];
+                    n_rows += __popc(g2);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+            gam |= ((__ballot(v[j] >= 0 && bit(fa, v[j])) >> base) & gmask) << (8 * j);
+        n_rows += __popcll(gam);
+        while (gam) {   // group-uniform: the next frontier row of every slot, NS loads in flight
+            typename V::T r[NS];
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                const unsigned m = (unsigned)(gam >> (8 * j)) & 0xffu;
+                const int32_t vk = __shfl(v[j], base + (m ? __ffs(m) - 1 : 0));
+                r[j] = m ? V::ld(lvl + (int64_t)vk * W + sub * WPL) : V::zero();
+                gam &= ~((u64)(m & (0u - m)) << (8 * j));
+            }
+#pragma unroll
+            for (int j = 0; j < NS; ++j) acc[j / E] |= r[j];
+        }
+        if (live) pos += E;
+        // atoms that covered or ran out of entries: their rows
+        const unsigned ll = (unsigned)((__ballot(live) >> base) & gmask);
+        const unsigned xl = (unsigned)((__ballot(live && pos >= end) >> base) & gmask);
+        const unsigned evl = (unsigned)((__ballot(ev) >> base) & gmask);
+        const unsigned hl = (unsigned)((__ballot(deg > kHeavyDegree) >> base) & gmask);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            if (!((ll >> (a * E)) & 1u)) continue;   // group-uniform
+            const bool out = (xl >> (a * E)) & 1u;
+            const bool hub = resid && ((hl >> (a * E)) & 1u);
+            const bool cov = (!out || hub) && early && group_all<G>(V::eq(acc[a], FULL));
+            if (!out && !cov) continue;
+            const int64_t ta = __shfl(t, base + a * E);
+            if (hub && !cov) {   // a residual hub: hgx_nf_pull_heavy pulls it by chunks, the hub finalise writes it
+                if (sub == a * E) set_bit(resid, ta);
+                if (my_a == a) live = false;
+                continue;
+            }
+            const typename V::T old = ((evl >> (a * E)) & 1u) ? V::ld(vis + ta * W + sub * WPL) : V::zero();
+            const typename V::T nw = acc[a] & ~old;
+            const bool mine = sub == a * E;   // the lane that holds the atom's scalars
+            if (group_any<G>(V::nz(nw))) {
+                V::st(lvl_next + ta * W + sub * WPL, nw);
+                V::st(vis + ta * W + sub * WPL, acc[a]);
+                const bool becomes_full = group_all<G>(V::eq(acc[a], FULL));
+                if (mine) {
+                    set_bit(fa_next, ta);
+                    if (!ev) set_bit(ever, ta);
+                    if (becomes_full) set_bit(full, ta);
+                    ++n_new;
+                    n_full += becomes_full;
+                    n_newdeg += (u64)deg;
+                    if (!becomes_full) n_newdeg_nf += (u64)deg;
+                }
+                if (cpart) fuse_add_cs<W>(cplanes, sub, cones, nw);
+            }
+            if (mine) {
+                ++n_cand;
+                n_vis += 2u * ev;   // vis rows read: when the atom was taken and again here
+            }
+            if (my_a == a) live = false;
+        }
+    }
+    if (sub != 0) n_rows = 0;   // n_ent / n_pins: each lane counted its own entry
+    wave_add_sh(ctr + cActiveLinks, n_ent);
+    wave_add_sh(ctr + cActivePins, n_pins);
+    wave_add_sh(ctr + cIncLight, n_ent);
+    wave_add_sh(ctr + cCand, n_cand);
+    wave_add_sh(ctr + cNewFull, n_full);
+    wave_add_sh(ctr + cVisLight, n_vis);
+    wave_add_sh(ctr + cNewLight, n_new);
+    wave_add_sh(ctr + cNewAtoms, n_new);
+    wave_add_sh(ctr + cNewDeg, n_newdeg);
+    wave_add_sh(ctr + cNewDegNF, n_newdeg_nf);
+    wave_add_sh(ctr + cNfRows, n_rows);
+    if (cpart) {
+        fuse_flush<W>(cplanes, sub, cones);
+        fuse_store<W>(cplanes, &cdone, cpart);
+    }
+}
+
+// The residual hubs of hgx_nf_pull_e (more than kHeavyDegree entries, not covered by the first kHeavyDegree):
+// their whole incidence by HeavyChunk as in hgx_atom_pull_heavy, pulled from the frontier rows -- the groups
+// of a workgroup share a chunk's entries, an LDS reduce, one atomicOr per chunk and word into hubacc;
+// hgx_hub_finalize writes the rows.  The workgroups stride over the chunk table and skip the chunks of
+// atoms without a residual bit (config 2: every listed hub covers within its first entries).
+template <int W>
+__global__ void __launch_bounds__(256) hgx_nf_pull_heavy(const HeavyChunk* __restrict__ chunks, int64_t n_chunks,
+                                                         const u64* __restrict__ resid,
+                                                         const int32_t* __restrict__ inc_row,
+                                                         const int32_t* __restrict__ inc_type, int32_t want_type,
+                                                         const int64_t* __restrict__ tgt_off,
+                                                         const int32_t* __restrict__ tgt_idx,
+                                                         const u64* __restrict__ fa, const u64* __restrict__ lvl,
+                                                         const u64* __restrict__ vis, const u64* __restrict__ ever,
+                                                         u64* __restrict__ hubacc, u64* __restrict__ ctr, FullMask fm,
+                                                         int flags) {
+    constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G;
+    constexpr int NG = 256 / G;
+    typedef Vec<WPL> V;
+    __shared__ u64 red[NG * W];
+    const int sub = threadIdx.x & (G - 1);
+    const int gi = threadIdx.x / G;
+    const typename V::T FULL = full_part<W>(fm, sub);
+    u64 n_ent = 0, n_pins = 0, n_rows = 0;
+    for (int64_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {   // block-uniform
+        const HeavyChunk c = chunks[ci];
+        if (!bit(resid, c.atom)) continue;
+        const int64_t n = c.end - c.beg;
+        const int64_t per = (n + NG - 1) / NG;
+        const int64_t b = c.beg + gi * per;
+        const int64_t e = b + per < c.end ? b + per : c.end;
+        const typename V::T old = bit(ever, c.atom) ? V::ld(vis + (int64_t)c.atom * W + sub * WPL) : V::zero();
+        typename V::T acc = V::zero();
+        if (b < e)   // group-uniform
+            nf_range<W>(b, e, inc_row, inc_type, want_type, tgt_off, tgt_idx, fa, lvl, FULL, old, acc, (flags & 2) != 0,
+                        n_ent, n_pins, n_rows);
+        V::st(red + gi * W + sub * WPL, acc);
+        __syncthreads();
+        for (int j = threadIdx.x; j < W; j += 256) {
+            u64 r = 0;
+            for (int k = 0; k < NG; ++k) r |= red[k * W + j];
+            if (r) atomicOr(hubacc + (int64_t)c.slot * W + j, r);
+        }
+        __syncthreads();   // red is rewritten by the next chunk
+    }
+    if (sub != 0) n_rows = 0;
+    wave_add_sh(ctr + cActiveLinks, n_ent);
+    wave_add_sh(ctr + cActivePins, n_pins);
+    wave_add_sh(ctr + cIncHeavy, n_ent);
+    wave_add_sh(ctr + cNfRows, n_rows);
+}
+
+// A sample of a dense level's outcome for the direct-pull rule of the next level (HGX_OPT_NF_PULL = 1):
+// one atom of every `stride` (a power of two; a hashed offset inside the stride).  Two counters that the
+// symmetric-mode dense kernels leave at zero carry it: cDirRows takes (sampled new atoms << 40) + the
+// bits of their rows (< 2^40: at most 2^20 sampled atoms of <= 1024 bits), cScanned the sampled atoms
+// with incidence that are not yet visited by every traversal (the next level's list).
+constexpr int64_t kNfSampleAtoms = 1 << 18;
+template <int W>
+__global__ void __launch_bounds__(256) hgx_level_sample(int64_t A, int stride, const u64* __restrict__ fa_next,
+                                                        const u64* __restrict__ lvl_next,
+                                                        const u64* __restrict__ full,
+                                                        const int64_t* __restrict__ inc_off, u64* __restrict__ ctr) {
+    u64 packed = 0, nf = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i * stride < A;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t t = i * stride + (int64_t)((((uint32_t)i * 0x9E3779B1u) >> 16) & (uint32_t)(stride - 1));
+        if (t >= A) continue;
+        if (bit(fa_next, t)) {
+            u64 bits = 0;
+            for (int w = 0; w < W; ++w) bits += (u64)__popcll(lvl_next[t * W + w]);
+            packed += (1ull << 40) + bits;
+        }
+        if (!bit(full, t) && inc_off[t + 1] > inc_off[t]) ++nf;
+    }
+    wave_add_sh(ctr + cDirRows, packed);
+    wave_add_sh(ctr + cScanned, nf);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4167,7 +4459,14 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         u64* slot = nullptr;
         uint32_t* cpart = nullptr;   // fused counts of the level's new rows: cblk block partials
         int32_t cblk = 0;
+        bool sampled = false;   // hgx_level_sample ran: cDirRows / cScanned carry its sample
     } pend[2];
+    // The direct-pull rule (HGX_OPT_NF_PULL = 1): the sample of the previous level
+    const int nf_opt = g->nf_pull;
+    const bool nf_eligible = sparse_ok && MODE == kSym && Lay<W>::G >= 4 && !ex && (g->bfs_flags & 256);
+    int nf_stride = 1;
+    while ((int64_t)nf_stride * 2 * kNfSampleAtoms <= A) nf_stride *= 2;
+    double samp_rows = 0, samp_bits = 0, samp_nf = 0;   // (zero: no sample, the rule does not select)
     auto cpart_size = [](int32_t blocks) { return sizeof(uint32_t) * (size_t)blocks * W * 64; };
     for (int k = 0; k < 2; ++k) {
         pend[k].h = h_sh + (size_t)k * kCtrBlock;
@@ -4204,6 +4503,13 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                 h_new[k] = 0;
                 for (int sh = 0; sh < kCtrShards; ++sh) h_new[k] += p.h[sh * kCtrStride + k];
             }
+        }
+        samp_rows = samp_bits = samp_nf = 0;
+        if (p.sampled) {   // the two borrowed counters go back to zero
+            samp_rows = (double)(h_new[cDirRows] >> 40);
+            samp_bits = (double)(h_new[cDirRows] & ((1ull << 40) - 1ull));
+            samp_nf = (double)h_new[cScanned];
+            h_new[cDirRows] = h_new[cScanned] = 0;
         }
         if (ex) {   // the group decides termination; the next level's push volume is my frontier's
             h_new[cNewAtoms] = p.new_global;
@@ -4262,8 +4568,26 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         if ((lflags & 16) && (int64_t)full_total * 16 < A) lflags &= ~4;   // adaptive full skip
         const bool opush = sparse && (MODE != kSym || (lflags & 32));
         // late dense level with few atoms left unfull: those pull from the frontier directly
-        const bool nfp = !sparse && sparse_ok && MODE == kSym && Lay<W>::G >= 4 && !ex && (lflags & 256) &&
-                         (lflags & 4) && 4 * (int64_t)(I_total - full_deg_total) < I_total;
+        bool nfp = !sparse && sparse_ok && MODE == kSym && Lay<W>::G >= 4 && !ex && (lflags & 256) &&
+                   (lflags & 4) && 4 * (int64_t)(I_total - full_deg_total) < I_total;
+        // ... or an earlier dense level whose listed atoms are predicted to cover after a few rows:
+        // the frontier's rows hold a share p of their bits, so about ln S / -ln(1 - p) independent rows
+        // cover S traversals, each at 1 + 2 / k transactions (k = arity - 1 frontier rows per entry and its
+        // two CSR lines); gather + pull costs the frontier's pins, a row per link and a row per entry
+        const bool nf_late = nfp;   // chosen by the old rule
+        if (!nfp && !sparse && nf_eligible && nf_opt == 2) nfp = true;
+        if (!nfp && !sparse && nf_eligible && nf_opt == 1 && samp_rows > 0 && samp_bits > 0) {
+            const double S = (double)bt.S, pbits = std::min(samp_bits / (samp_rows * S), 0.999);
+            const double need = std::log(S) / -std::log1p(-pbits);
+            const double k = std::max((double)g->P / (double)std::max<int64_t>(M, 1) - 1.0, 1.0);
+            const double I_nf = (double)(I_total - full_deg_total);
+            const double direct = std::min(samp_nf * nf_stride * need * (1.0 + 2.0 / k), I_nf * (k + 2.0));
+            const double old_cost = std::min((double)push_volume_nf, (double)g->P) + (double)M + I_nf;
+            nfp = direct < old_cost;
+            if (trace)
+                std::fprintf(stderr, "[hgx bfs] level %d direct-pull rule: p %.4f need %.1f listed %.0f direct %.3g "
+                             "gather+pull %.3g -> %d\n", d, pbits, need, samp_nf * nf_stride, direct, old_cost, (int)nfp);
+        }
         // dense level over a frontier whose rows fit the Infinity Cache: the frontier-code pull (bit 17)
         const int4* fcrec = nullptr;
         if (!nfp && !sparse && MODE == kSym && Lay<W>::G >= 4 && !ex && (lflags & kFc) &&
@@ -4336,14 +4660,46 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                 hgx_nonfull_list<<<grid_for(ceil_div(A, 64), 256, 2048), 256, 0, s>>>(A, full, hasinc, clist, n_list);
                 HGX_CHECK_LAUNCH();
                 constexpr int nf_grid = 4096;
-                if (fuse_ok && fuse_rows_ok(A, nf_grid, 256 / Lay<W>::G)) {
-                    lv_cblk = nf_grid;
+                constexpr int G = Lay<W>::G;
+                // the cover test's step in entries (DESIGN 3.1 item 12 has the steps measured): with
+                // HGX_OPT_NF_PULL = 0 the group's G entries; else 2 where the rule (or value 2) chose the
+                // level, 1 on the late levels of the old rule; HGX_NF_E overrides (A/B builds)
+                const int nf_e = nf_opt == 0 ? G : ab_int("HGX_NF_E", nf_late ? 1 : 2);
+                const bool stepped = nf_e == 1 || nf_e == 2 || (nf_e == 4 && G > 4);   // hgx_nf_pull_e
+                // hubs: hgx_nf_pull_e leaves those not covered by their first kHeavyDegree entries to the
+                // chunk kernel and the hub finalise (whose blocks own the partial rows after the pull's)
+                const bool hubs = stepped && g->n_chunks > 0;
+                if (fuse_ok && fuse_rows_ok(A, nf_grid, 256 / G) &&
+                    (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / G))) {
+                    lv_cblk = nf_grid + (hubs ? hub_grid : 0);
                     lv_cpart = (uint32_t*)g->alloc(cpart_size(lv_cblk));
                 }
-                hgx_nf_pull<W><<<nf_grid, 256, 0, s>>>(clist, n_list, g->inc_off, g->inc_row, g->inc_type, want_type,
-                                                       g->tgt_off, g->tgt_idx, fa, lvl, vis, ever, full, lvl_next,
-                                                       fa_next, c, fm, lflags, lv_cpart);
+                u64* resid = nullptr;
+                if (hubs) {
+                    resid = (u64*)g->alloc(bm_bytes);
+                    HGX_HIP(hipMemsetAsync(resid, 0, bm_bytes, s));
+                }
+#define HGX_NF_ARGS clist, n_list, g->inc_off, g->inc_row, g->inc_type, want_type, g->tgt_off, g->tgt_idx, fa, lvl, vis, \
+                    ever, full, lvl_next, fa_next, c, fm, lflags, lv_cpart
+                // (a test per entry with 8 atoms in flight spills: 4 entry slots there)
+                if (nf_e == 1) hgx_nf_pull_e<W, 1, 4><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
+                else if (nf_e == 2) hgx_nf_pull_e<W, 2, G><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
+                else if (stepped) hgx_nf_pull_e<W, G / 2, G><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
+                else hgx_nf_pull<W><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS);
+#undef HGX_NF_ARGS
                 HGX_CHECK_LAUNCH();
+                if (hubs) {
+                    const int hgrid = (int)std::min<int64_t>(g->n_chunks, 2048);
+                    hgx_nf_pull_heavy<W><<<hgrid, 256, 0, s>>>(g->chunks, g->n_chunks, resid, g->inc_row, g->inc_type,
+                                                                want_type, g->tgt_off, g->tgt_idx, fa, lvl, vis, ever,
+                                                                hubacc, c, fm, lflags);
+                    HGX_CHECK_LAUNCH();
+                    hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(
+                        g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis, ever, full, lvl_next, fa_next, c, fm,
+                        lv_cpart ? lv_cpart + (size_t)nf_grid * W * 64 : nullptr);
+                    HGX_CHECK_LAUNCH();
+                    g->release(resid, bm_bytes);   // stream-ordered reuse
+                }
                 tm.stop(e2);
             }
         } else if (opush) {
@@ -4561,6 +4917,13 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         pn.slot = flag_slot;
         pn.cpart = lv_cpart;
         pn.cblk = lv_cblk;
+        // a dense level's sample for the next level's direct-pull rule
+        pn.sampled = !flag_level && !sparse && nf_eligible && nf_opt == 1 && d + 1 < maxd;
+        if (pn.sampled) {
+            hgx_level_sample<W><<<grid_for(ceil_div(A, nf_stride), 256, 4096), 256, 0, s>>>(
+                A, nf_stride, fa_next, lvl_next, full, g->inc_off, c);
+            HGX_CHECK_LAUNCH();
+        }
         if (!flag_level) {
             tm.break_chain();
             HGX_HIP(hipMemcpyAsync(pn.h, c, sizeof(u64) * kCtrBlock, hipMemcpyDeviceToHost, s));

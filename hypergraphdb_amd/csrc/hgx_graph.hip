@@ -329,6 +329,7 @@ int hgx_graph_context(hgx_graph* g, hgx_graph** out) {
     c->xb_static = g->xb_static;
     c->sp_budget_bytes = g->sp_budget_bytes;
     c->count_fused = g->count_fused;
+    c->nf_pull = g->nf_pull;
     c->ranks_ordered = g->ranks_ordered; c->q_inline = g->q_inline;
     c->q_coalesce = g->q_coalesce; c->q_coalesce_max = g->q_coalesce_max;
     guard.c = nullptr;
@@ -585,6 +586,9 @@ int hgx_set_option(hgx_graph* g, int32_t option, int64_t value) {
     } else if (option == HGX_OPT_COUNT_FUSED) {
         if (value != 0 && value != 1) fail(HGX_E_INVALID, "hgx_set_option: HGX_OPT_COUNT_FUSED is 0 or 1");
         g->count_fused = (int32_t)value;
+    } else if (option == HGX_OPT_NF_PULL) {
+        if (value < 0 || value > 2) fail(HGX_E_INVALID, "hgx_set_option: HGX_OPT_NF_PULL is 0, 1 or 2");
+        g->nf_pull = (int32_t)value;
     } else fail(HGX_E_INVALID, "hgx_set_option: unknown option");
     HGX_API_END
 }

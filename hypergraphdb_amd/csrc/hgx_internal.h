@@ -289,6 +289,7 @@ struct hgx_graph {
     int32_t xb_flat = -1, xb_static = -1;           // partition broadcast pack variants (-1 = default)
     int64_t sp_budget_bytes = (int64_t)48 << 30;    // HGX_OPT_SP_BUDGET (hgx_paths.h): shortest-path working arrays
     int32_t count_fused = 1;                        // HGX_OPT_COUNT_FUSED: dense-level kernels count the rows they store
+    int32_t nf_pull = 1;                            // HGX_OPT_NF_PULL: 0 = late levels only, 8-entry step; 1 = the rule; 2 = every eligible level
     unsigned long long* co_vis = nullptr;           // multi-workgroup stage: per-seed visited bitmaps (zero between calls)
     unsigned long long* sc_tab = nullptr;           // order-exact grid stage: level hash, word / key counts (empty between calls)
     int64_t co_vis_seeds = 0, co_pcap = 0;          //   seeds they hold; pair-list capacity (grown on demand)

@@ -548,6 +548,13 @@ int  hgx_shard_graph_create(const hgx_shard *s, int32_t device, hgx_graph **out)
  * 0 = every dense level is counted by the readout's pass (A/B; the results are the same).
  * hgx_bfs_stats.count_pass_levels tells how many levels of a call were left to the pass. */
 #define HGX_OPT_COUNT_FUSED  23
+/* HGX_OPT_NF_PULL (default 1): the direct pull of hgx_bfs_batch's dense symmetric-mode levels (hgx_nf_pull:
+ * the atoms not yet visited by every traversal pull from the frontier rows of their neighbours, no link
+ * gather).  0 = only when the visited-by-all atoms hold three quarters of the incidence, the cover test
+ * once per 8 entries; 1 = also when the bits of the frontier's rows predict that an atom is covered after
+ * a few links, the cover test after every entry; 2 = every eligible dense level (tests, A/B).  The results
+ * are the same for every value. */
+#define HGX_OPT_NF_PULL      24
 /* Coalescing statistics of a graph since its creation: device batches run by the packed pattern path
  * and caller batches they served (caller / device = the mean coalescing factor). */
 int  hgx_query_coalesce_stats(hgx_graph *g, int64_t *device_batches, int64_t *caller_batches);

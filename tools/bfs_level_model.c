@@ -1,0 +1,137 @@
+/* CPU model of the batched BFS level engine's work: the config-2 / config-4
+ * generator of hgx_gen.c, S-bit rows, incidence lists deduplicated and ascending, hubs at degree > 512,
+ * the cover test acc | vis == FULL.  Per level it prints the frontier, the active links and frontier pins
+ * (what the link gather reads), and per exit step E = 1/2/4/8/16 the lf rows a pull of gather + pull
+ * reads, the frontier rows a direct pull reads (own row included; entries) and the links whose lf row
+ * any pull reads -- light atoms and hubs apart.
+ *   gcc -O3 -fopenmp -o bfs_level_model tools/bfs_level_model.c hypergraphdb_amd/csrc/hgx_gen.c -lm
+ *   ./bfs_level_model [scale=0.01] [sources=1024] [depth=4] [nodes=10e6*scale] [links=40e6*scale]   */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+int64_t hgx_gen_hypergraph_offsets(int64_t M, int32_t lo, int32_t hi, uint64_t seed, int64_t *tgt_off);
+int hgx_gen_hypergraph_fill(int64_t N, int64_t M, int32_t lo, int32_t hi, double gamma, int32_t n_types,
+                            uint64_t seed, const int64_t *tgt_off, int32_t *tgt_idx, int32_t *link_type);
+int hgx_gen_sources(int64_t n, int64_t P, const int32_t *tgt_idx, int64_t k, uint64_t seed, int32_t *out);
+
+enum { NE = 5, HEAVY = 512 };
+static const int ES[NE] = {1, 2, 4, 8, 16};
+typedef uint64_t u64;
+
+int main(int argc, char **argv) {
+    const double scale = argc > 1 ? atof(argv[1]) : 0.01;
+    const int S = argc > 2 ? atoi(argv[2]) : 1024, depth = argc > 3 ? atoi(argv[3]) : 4, W = (S + 63) / 64;
+    const int64_t N = argc > 4 ? atoll(argv[4]) : (int64_t)(10e6 * scale), M = argc > 5 ? atoll(argv[5]) : (int64_t)(40e6 * scale);
+    int64_t *off = malloc(sizeof(int64_t) * (M + 1));
+    const int64_t P = hgx_gen_hypergraph_offsets(M, 2, 8, 42, off);
+    int32_t *tg = malloc(sizeof(int32_t) * P), *lt = malloc(sizeof(int32_t) * M), *seeds = malloc(sizeof(int32_t) * S);
+    if (hgx_gen_hypergraph_fill(N, M, 2, 8, 2.1, 1, 42, off, tg, lt) || hgx_gen_sources(N, P, tg, S, 7, seeds)) return 1;
+    /* incidence: links ascending, a link listed once per atom */
+    int64_t *io = calloc(N + 1, sizeof(int64_t));
+    int32_t *last = malloc(sizeof(int32_t) * N), *inc = NULL;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass) {
+            for (int64_t v = 0; v < N; ++v) io[v + 1] += io[v];
+            inc = malloc(sizeof(int32_t) * (io[N] + 1));
+        }
+        memset(last, 0xff, sizeof(int32_t) * N);
+        for (int64_t L = 0; L < M; ++L)
+            for (int64_t p = off[L]; p < off[L + 1]; ++p) {
+                const int32_t v = tg[p];
+                if (last[v] == (int32_t)L) continue;
+                last[v] = (int32_t)L;
+                if (pass) inc[io[v]++] = (int32_t)L; else ++io[v + 1];
+            }
+        if (pass) {
+            for (int64_t v = N; v > 0; --v) io[v] = io[v - 1];
+            io[0] = 0;
+        }
+    }
+    u64 FULL[16] = {0};
+    for (int s = 0; s < S; ++s) FULL[s >> 6] |= 1ull << (s & 63);
+    u64 *vis = calloc((size_t)N * W, 8), *lvl = calloc((size_t)N * W, 8), *nxt = calloc((size_t)N * W, 8);
+    uint8_t *F = calloc(N, 1), *Fn = calloc(N, 1), *used = malloc((size_t)M * NE);
+    for (int s = 0; s < S; ++s) {
+        lvl[(size_t)seeds[s] * W + (s >> 6)] |= 1ull << (s & 63);
+        vis[(size_t)seeds[s] * W + (s >> 6)] |= 1ull << (s & 63);
+        F[seeds[s]] = 1;
+    }
+    printf("N %lld M %lld P %lld I %lld S %d\n", (long long)N, (long long)M, (long long)P, (long long)io[N], S);
+    for (int d = 0; d < depth; ++d) {
+        int64_t nf = 0, alinks = 0, fpins = 0, nnew = 0, cand[2] = {0, 0}, k1[2] = {0, 0}, cover[2] = {0, 0};
+        int64_t lf[2][NE] = {{0}}, rows[2][NE] = {{0}}, ent[2][NE] = {{0}};
+        for (int64_t v = 0; v < N; ++v) nf += F[v];
+#pragma omp parallel for reduction(+ : alinks, fpins) schedule(static, 4096)
+        for (int64_t L = 0; L < M; ++L) {
+            int c = 0;
+            for (int64_t p = off[L]; p < off[L + 1]; ++p) c += F[tg[p]];
+            alinks += c > 0;
+            fpins += c;
+        }
+        memset(used, 0, (size_t)M * NE);
+        memset(nxt, 0, (size_t)N * W * 8);
+#pragma omp parallel for schedule(dynamic, 256) reduction(+ : nnew, cand[:2], k1[:2], cover[:2], lf[:2][:NE], rows[:2][:NE], ent[:2][:NE])
+        for (int64_t t = 0; t < N; ++t) {
+            const int64_t b = io[t], e = io[t + 1], deg = e - b;
+            u64 *vt = vis + (size_t)t * W, acc[16] = {0};
+            int full = 1;
+            for (int w = 0; w < W; ++w) full &= vt[w] == FULL[w];
+            Fn[t] = 0;
+            if (deg == 0 || full) continue;
+            const int h = deg > HEAVY;
+            int64_t kc = deg;   /* entries until acc | vis covers (deg: never) */
+            int covered = 0;
+            for (int64_t i = 0; i < deg && !covered; ++i) {
+                const int32_t L = inc[b + i];
+                for (int64_t p = off[L]; p < off[L + 1]; ++p)
+                    if (F[tg[p]]) for (int w = 0; w < W; ++w) acc[w] |= lvl[(size_t)tg[p] * W + w];
+                covered = 1;
+                for (int w = 0; w < W; ++w) covered &= (acc[w] | vt[w]) == FULL[w];
+                if (covered) kc = i + 1;
+            }
+            ++cand[h];
+            cover[h] += covered;
+            k1[h] += kc;
+            for (int64_t i = 0; i < deg && i < (kc + 15) / 16 * 16; ++i) {
+                const int32_t L = inc[b + i];
+                int c = 0;
+                for (int64_t p = off[L]; p < off[L + 1]; ++p) c += F[tg[p]];
+                for (int k = 0; k < NE; ++k) {
+                    const int64_t stop = (kc + ES[k] - 1) / ES[k] * ES[k];
+                    if (i >= stop) continue;
+                    ++ent[h][k];
+                    rows[h][k] += c;
+                    if (c) { ++lf[h][k]; used[(size_t)L * NE + k] = 1; }
+                }
+            }
+            int any = 0;
+            for (int w = 0; w < W; ++w) {
+                const u64 nw = acc[w] & ~vt[w];
+                nxt[(size_t)t * W + w] = nw;
+                any |= nw != 0;
+            }
+            if (any) { Fn[t] = 1; ++nnew; for (int w = 0; w < W; ++w) vt[w] |= acc[w]; }
+        }
+        printf("level %d: frontier %lld atoms, active links %lld (%.1f%%), frontier pins %lld, new atoms %lld\n", d,
+               (long long)nf, (long long)alinks, 100.0 * alinks / M, (long long)fpins, (long long)nnew);
+        for (int h = 0; h < 2; ++h) {
+            printf("  %s: %lld not full, %lld cover, entries to cover (sum) %lld\n", h ? "hubs " : "light", (long long)cand[h],
+                   (long long)cover[h], (long long)k1[h]);
+            for (int k = 0; k < NE; ++k)
+                printf("    E=%-2d entries %lld  lf rows %lld  direct rows %lld\n", ES[k], (long long)ent[h][k],
+                       (long long)lf[h][k], (long long)rows[h][k]);
+        }
+        for (int k = 0; k < NE; ++k) {
+            int64_t u = 0;
+            for (int64_t L = 0; L < M; ++L) u += used[(size_t)L * NE + k];
+            printf("  E=%-2d links whose row a pull reads %lld (%.1f%% of the active links)\n", ES[k], (long long)u,
+                   alinks ? 100.0 * u / alinks : 0.0);
+        }
+        u64 *x = lvl; lvl = nxt; nxt = x;
+        uint8_t *y = F; F = Fn; Fn = y;
+        if (!nnew) break;
+    }
+    return 0;
+}

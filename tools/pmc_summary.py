@@ -35,7 +35,7 @@ from collections import defaultdict
 
 # kernels that implement one engine kind (HGX_K_* of include/hgx.h): the tile-staged dense kernels
 # report under the kind's name so bench.py finds their PMC bytes
-KIND = {"hgx_link_gather2": "hgx_link_gather", "hgx_atom_pull2": "hgx_atom_pull"}
+KIND = {"hgx_link_gather2": "hgx_link_gather", "hgx_atom_pull2": "hgx_atom_pull", "hgx_nf_pull_e": "hgx_nf_pull"}
 
 
 def short(name):
