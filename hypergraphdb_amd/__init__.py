@@ -5,7 +5,7 @@ This package is the host-side mirror of the reference interfaces on that path:
   snapshot.HyperGraphSnapshot   the store snapshot (bipartite CSR on the device)
   algorithms                    DefaultALGenerator / HGBreadthFirstTraversal / bfs_batch
   query                         hg.and/or/type/incident/orderedLink, GpuAndToQuery, GpuOrToQuery, pattern_batch,
-                                pattern_batch_dnf (include/hgx_dnf.h)
+                                pattern_batch_dnf (include/hgx_dnf.h); hg.not_ on its clauses (include/hgx_not.h)
   classics                      GraphClassics.dijkstra / shortest_paths (include/hgx_paths.h);
                                 hop_paths -> HopPaths, BfsResult.paths / depths / predecessors: unit-weight
                                 shortest paths read out of a batched BFS (include/hgx_hops.h)
@@ -16,7 +16,7 @@ from .algorithms import (AtomTypeCondition, BfsResult, DefaultALGenerator, HGBre
                          HGException, bfs_batch)
 from .classics import GraphClassics, LinkWeights, ShortestPathsResult, hop_paths, shortest_paths  # noqa: F401
 from .query import (And, ArityCondition, GpuAndToQuery, GpuOrToQuery, HGQueryConfiguration, LinkCondition,  # noqa: F401
-                    Or, PositionedIncidentCondition, TypePlusCondition, find_all, hg, pattern_batch,
+                    Not, Or, PositionedIncidentCondition, TypePlusCondition, find_all, hg, pattern_batch,
                     pattern_batch_dnf, to_dnf)
 from .snapshot import HyperGraphSnapshot, export_store, rank_handles, read_snapshot, write_snapshot  # noqa: F401
 

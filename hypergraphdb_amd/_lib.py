@@ -87,6 +87,9 @@ EXPORTED_PATHS = (
 # Every symbol include/hgx_dnf.h declares (checked by tests/test_dnf_ref.py without a GPU).
 EXPORTED_DNF = ("hgx_pattern_batch_dnf", "hgx_query_result_union_stats")
 
+# Every symbol include/hgx_not.h declares (checked by tests/test_not_ref.py without a GPU).
+EXPORTED_NOT = ("hgx_pattern_batch_dnf_not", "hgx_query_result_not_stats")
+
 # Every symbol include/hgx_hops.h declares (checked by tests/test_hop_ref.py without a GPU).
 EXPORTED_HOPS = (
     "hgx_bfs_result_paths", "hgx_hop_paths_info", "hgx_hop_paths_offsets", "hgx_hop_paths_read", "hgx_hop_paths_stats",
@@ -261,6 +264,11 @@ def lib():
         "hgx_pattern_batch_dnf": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp)], C.c_int),
         "hgx_query_result_union_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)], C.c_int),
+        # include/hgx_not.h
+        "hgx_pattern_batch_dnf_not": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                       C.POINTER(vp)], C.c_int),
+        "hgx_query_result_not_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)], C.c_int),
         # include/hgx_hops.h
         "hgx_bfs_result_paths": ([vp, vp, vp, i32, C.POINTER(vp)], C.c_int),
         "hgx_hop_paths_info": ([vp, C.POINTER(i32), C.POINTER(i64)], C.c_int),
@@ -273,6 +281,8 @@ def lib():
         "hgx_bfs_result_predecessor_row": ([vp, i32, i64, i64, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
+        if LIB_VARIANT and not hasattr(L, name):
+            continue   # an A/B variant built from older sources: it lacks the entries added since
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = res

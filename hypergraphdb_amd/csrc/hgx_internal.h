@@ -27,6 +27,7 @@
 
 #include "../../include/hgx_dnf.h"
 #include "../../include/hgx_hops.h"
+#include "../../include/hgx_not.h"
 #include "../../include/hgx_paths.h"
 
 namespace hgx {
@@ -465,6 +466,54 @@ struct UnionArgs {
 size_t union_temp_bytes(int64_t cap, hipStream_t s);
 // Enqueues the union on s: no synchronisation, nothing read back by the host.
 void union_launch(const UnionArgs& a, hipStream_t s);
+
+// The negation program of a DNF batch (hgx_pattern_batch_dnf_not, include/hgx_not.h) as the caller handed
+// it over; not_validate fills the totals.
+struct NotProgram {
+    const int64_t* neg_off = nullptr;    // [n_clauses + 1]
+    const int64_t* term_off = nullptr;   // [n_negs + 1]
+    const int64_t* lit_off = nullptr;    // [n_terms + 1]
+    const int32_t* lit = nullptr;        // [4 n_lits] (kind, polarity, op_beg, op_end)
+    const int32_t* ops = nullptr;        // [n_ops]
+    int64_t n_ops = 0, n_negs = 0, n_terms = 0, n_lits = 0;
+};
+// Every offset, operand range, atom id and kind of the program, on the host (hgx_not.hip): fails with
+// HGX_E_INVALID / HGX_E_UNSUPPORTED naming the query, the clause and the negation.  A = atoms of the graph.
+void not_validate(int64_t A, int32_t n_queries, const int64_t* clause_off, NotProgram& p);
+// Its device copy (neg_off == nullptr: the batch has no negation).
+struct NotDev {
+    const int64_t* neg_off = nullptr;
+    const int64_t* term_off = nullptr;
+    const int64_t* lit_off = nullptr;
+    const int4* lit = nullptr;
+    const int32_t* ops = nullptr;
+};
+// The filter stage of a DNF batch with negations (hgx_not.hip), between the clause stage and
+// the union: the clause hits that pass their clause's negations, compacted into hits_out / run_out in the
+// layout the union reads.  flag / pre / tmp are the union's keep / pre / tmp (it overwrites them afterwards).
+struct NotArgs {
+    NotDev prog;
+    int32_t n_clauses;
+    const int64_t* run_off;      // [n_clauses + 1] hit offsets of each clause
+    const int32_t* hits;         // [cap] the clause hits (link atoms)
+    int64_t cap;
+    const int64_t* stat;         // [8] statistics of the clause stage: [2] overflow
+    int64_t M;                   // the snapshot's link rows
+    const int32_t* link_atom;
+    const int64_t* tgt_off;
+    const int32_t* tgt_idx;
+    const int32_t* link_type;
+    uint8_t* flag;               // [cap + 1] 1 = the hit passes
+    int64_t* pre;                // [cap + 1] exclusive prefix sum of flag
+    void* tmp;                   // scan temporary storage (union_temp_bytes)
+    size_t tmp_bytes;
+    int32_t* hits_out;           // [cap] the hits that pass, each clause ascending
+    int64_t* run_out;            // [n_clauses + 1] their offsets
+    unsigned long long* ctr;     // [8] tested, rejected, targets read, types read, row-search probes
+    unsigned long long* out_ctr; // [8] mapped: ctr
+};
+// Enqueues the filter on s: no synchronisation, nothing read back by the host.
+void not_launch(const NotArgs& a, hipStream_t s);
 }  // namespace hgx
 
 // One batch (<= 1024 seeds) of a batched BFS and the result object of hgx_bfs_batch (hgx_bfs.hip makes and

@@ -1069,6 +1069,9 @@ struct hgx_query_result {
     // hgx_pattern_batch_dnf: clause hits before the union, ids kept, device ms and algorithmic bytes of it
     int64_t clause_hits = 0, kept = 0;
     double ms_union = 0, bytes_union = 0;
+    // hgx_pattern_batch_dnf_not: clause hits the filter tested / rejected, device ms and algorithmic bytes of it
+    int64_t hits_tested = 0, hits_rejected = 0;
+    double ms_not = 0, bytes_not = 0;
 };
 
 // A packed batch resident in device memory (hgx_query_set_create), in the staging layout of the
@@ -1367,6 +1370,9 @@ struct Front {
     int32_t n_or = -1;           //   Or queries of the batch (-1: a plain batch)
     const int64_t* clause_off_h = nullptr;
     const int64_t* clause_off = nullptr;   //   its device copy
+    // ... with negations (hgx_pattern_batch_dnf_not): the validated program goes up with the conditions too
+    const NotProgram* neg_h = nullptr;
+    NotDev neg;                            //   its device copy
 };
 
 // Buffers taken from the graph pool for one call, released on every exit path.
@@ -1387,6 +1393,7 @@ struct Events {
     hgx_graph* g = nullptr;
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t u = nullptr;   // start of the union stage (DNF batches only: taken on first use)
+    hipEvent_t nt = nullptr;  // start of the negation filter (DNF batches with negations only)
     bool on = false;
     void init(hgx_graph* gg) {
         g = gg;
@@ -1402,22 +1409,25 @@ struct Events {
         }
     }
     void rec(int i, hipStream_t s) { if (on) HGX_HIP(hipEventRecord(e[i], s)); }
-    void rec_union(hipStream_t s) {
+    void rec_extra(hipEvent_t& x, hipStream_t s) {
         if (!on) return;
-        if (!u) {
+        if (!x) {
             if (!g->ev_pool.empty()) {
-                u = g->ev_pool.back();
+                x = g->ev_pool.back();
                 g->ev_pool.pop_back();
             } else {
-                HGX_HIP(hipEventCreate(&u));
+                HGX_HIP(hipEventCreate(&x));
             }
         }
-        HGX_HIP(hipEventRecord(u, s));
+        HGX_HIP(hipEventRecord(x, s));
     }
+    void rec_union(hipStream_t s) { rec_extra(u, s); }
+    void rec_not(hipStream_t s) { rec_extra(nt, s); }
     ~Events() {
         for (int i = 0; i < 4; ++i)
             if (e[i]) g->ev_pool.push_back(e[i]);
         if (u) g->ev_pool.push_back(u);
+        if (nt) g->ev_pool.push_back(nt);
     }
 };
 
@@ -1443,6 +1453,15 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
                  o_poff = u.take(bytes_of(nb.p_off)), o_pat = u.take(bytes_of(nb.pattern)),
                  o_nop = u.take(bytes_of(nb.nop));
     const size_t o_cl = f.n_or >= 0 ? u.take(sizeof(int64_t) * ((size_t)f.n_or + 1)) : 0;
+    const NotProgram* np = f.neg_h;
+    size_t o_ng = 0, o_nt = 0, o_nl = 0, o_nr = 0, o_no = 0;
+    if (np) {
+        o_ng = u.take(sizeof(int64_t) * ((size_t)n + 1));
+        o_nt = u.take(sizeof(int64_t) * ((size_t)np->n_negs + 1));
+        o_nl = u.take(sizeof(int64_t) * ((size_t)np->n_terms + 1));
+        o_nr = u.take(sizeof(int32_t) * 4 * (size_t)np->n_lits);
+        o_no = u.take(sizeof(int32_t) * (size_t)np->n_ops);
+    }
     char* h = (char*)g->pinned_buf(u.off);
     auto put = [&](size_t o, const auto& v) {
         if (!v.empty()) std::memcpy(h + o, v.data(), sizeof(v[0]) * v.size());
@@ -1455,6 +1474,14 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     put(o_pat, nb.pattern);
     put(o_nop, nb.nop);
     if (f.n_or >= 0) std::memcpy(h + o_cl, f.clause_off_h, sizeof(int64_t) * ((size_t)f.n_or + 1));
+    if (np) {
+        const int64_t zero = 0;   // (a program without terms has no lit_off)
+        std::memcpy(h + o_ng, np->neg_off, sizeof(int64_t) * ((size_t)n + 1));
+        std::memcpy(h + o_nt, np->term_off, sizeof(int64_t) * ((size_t)np->n_negs + 1));
+        std::memcpy(h + o_nl, np->n_terms ? np->lit_off : &zero, sizeof(int64_t) * ((size_t)np->n_terms + 1));
+        if (np->n_lits) std::memcpy(h + o_nr, np->lit, sizeof(int32_t) * 4 * (size_t)np->n_lits);
+        if (np->n_ops) std::memcpy(h + o_no, np->ops, sizeof(int32_t) * (size_t)np->n_ops);
+    }
     char* d = (char*)sc.take(u.off);
     f.plan = (QPlan*)sc.take(sizeof(QPlan) * n);
     f.nch = (int32_t*)sc.take(sizeof(int32_t) * (n + 1));
@@ -1468,6 +1495,13 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     f.poff = (const int64_t*)(d + o_poff);
     f.pat = (const int32_t*)(d + o_pat);
     if (f.n_or >= 0) f.clause_off = (const int64_t*)(d + o_cl);
+    if (np) {
+        f.neg.neg_off = (const int64_t*)(d + o_ng);
+        f.neg.term_off = (const int64_t*)(d + o_nt);
+        f.neg.lit_off = (const int64_t*)(d + o_nl);
+        f.neg.lit = (const int4*)(d + o_nr);
+        f.neg.ops = (const int32_t*)(d + o_no);
+    }
     f.cond_bytes = 20.0 * nb.anchors.size() + 4.0 * nb.types.size() + 4.0 * nb.pos.size() +
                    4.0 * nb.pattern.size() + (double)sizeof(QDesc) * n;
     // the single-pass pipeline: the plan + per-block candidate totals
@@ -1594,10 +1628,11 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         u64* ctr = (u64*)w.take(sizeof(u64) * kQShards * kQStride);
         // result area in mapped host memory, written by the kernels (no copy back):
         // stat[8] | ctr[8] | q_off[nq+1] | ids[capK]      (a DNF batch: ctr[12], the union's four counters
-        // after the match's)
+        // after the match's; with negations ctr[20], the filter's eight after those)
         const bool dnf = f.n_or >= 0;
         const int32_t nq = dnf ? f.n_or : n;   // queries of the result (a DNF batch: n counts its clauses)
-        const size_t m_stat = 0, m_ctr = 64, m_qoff = dnf ? 160 : 128;
+        const bool neg = dnf && f.neg.neg_off;   // ... with negations: the filter's eight counters after the union's
+        const size_t m_stat = 0, m_ctr = 64, m_nctr = 160, m_qoff = dnf ? (neg ? 224 : 160) : 128;
         const size_t m_ids = m_qoff + ((8 * (size_t)(nq + 1) + 15) & ~(size_t)15);
         char* hm = (char*)g->mapped_buf(m_ids + 4 * (size_t)capK);
         void* hmd = nullptr;
@@ -1630,6 +1665,32 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             un.tmp_bytes = union_temp_bytes(capK, s);
             un.tmp = w.take(un.tmp_bytes);
             un.ctr = (u64*)w.take(sizeof(u64) * 4);
+        }
+        // negations: the filter compacts the clause hits that pass into a second hit array and the union
+        // reads that one (hgx_not.hip); its flags, prefix sums and scan storage are the union's
+        NotArgs na{};
+        if (neg) {
+            na.prog = f.neg;
+            na.n_clauses = n;
+            na.run_off = qoff_d;
+            na.hits = ids_d;
+            na.cap = capK;
+            na.stat = stat_d;
+            na.M = g->M;
+            na.link_atom = g->link_atom;
+            na.tgt_off = g->tgt_off;
+            na.tgt_idx = g->tgt_idx;
+            na.link_type = g->link_type;
+            na.flag = un.keep;
+            na.pre = un.pre;
+            na.tmp = un.tmp;
+            na.tmp_bytes = un.tmp_bytes;
+            na.hits_out = (int32_t*)w.take(sizeof(int32_t) * (size_t)capK);
+            na.run_out = (int64_t*)w.take(sizeof(int64_t) * ((size_t)n + 1));
+            na.ctr = (u64*)w.take(sizeof(u64) * 8);
+            na.out_ctr = (u64*)(rd + m_nctr);
+            un.run_off = na.run_out;
+            un.hits = na.hits_out;
         }
         const int64_t nbp = std::max<int64_t>(1, ceil_div(capC, kPlaceChunks));
         // derived flat index: no scan launch between the front kernel and the match (its counter shards
@@ -1687,6 +1748,10 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
                                                              0, 0, 0, nullptr, 0);
             HGX_CHECK_LAUNCH();
         }
+        if (neg) {
+            ev.rec_not(s);
+            not_launch(na, s);
+        }
         if (dnf) {
             ev.rec_union(s);
             union_launch(un, s);
@@ -1743,6 +1808,25 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
                 float c = 0;
                 HGX_HIP(hipEventElapsedTime(&c, ev.u, ev.e[3]));
                 r->ms_union = c;
+            }
+        }
+        if (neg) {
+            // algorithmic bytes of the filter: per clause hit its id read and its flag written,
+            // read by the scan and by the compaction, and its 8-byte prefix; per tested hit the offset pair,
+            // 4 B per row-search probe, per target and per type read; per hit that passes the id written; the
+            // program once; the run offsets read and written
+            const u64* nc = (const u64*)(hm + m_nctr);
+            const NotProgram& np = *f.neg_h;
+            const double H0 = (double)stat[6] + (double)nc[1];   // hits before the filter
+            r->hits_tested = (int64_t)nc[0];
+            r->hits_rejected = (int64_t)nc[1];
+            r->bytes_not = 15.0 * H0 + 16.0 * (double)nc[0] + 4.0 * ((double)nc[2] + (double)nc[3] + (double)nc[4]) +
+                           4.0 * (double)stat[6] + 8.0 * ((double)n + 1 + (double)np.n_negs + 1 + (double)np.n_terms + 1) +
+                           16.0 * (double)np.n_lits + 4.0 * (double)np.n_ops + 16.0 * ((double)n + 1);
+            if (ev.on) {
+                float c = 0;
+                HGX_HIP(hipEventElapsedTime(&c, ev.nt, ev.u));
+                r->ms_not = c;
             }
         }
         if (prof)
@@ -1813,7 +1897,7 @@ int run_batch(hgx_graph* g, int32_t n, NormBatch& nb, hgx_query_result** out) {
 // clause hits in device memory; the union stage (hgx_union.hip) writes the n_or results.  Takes the graph
 // mutex itself, like run_batch_with (no cross-thread coalescing).
 int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t n, NormBatch& nb,
-                  hgx_query_result** out) {
+                  hgx_query_result** out, const NotProgram* neg = nullptr) {
     HGX_API_BEGIN
     const bool prof = trace_env("HGX_QUERY_PROFILE");
     const double t0 = now_ms();
@@ -1831,6 +1915,7 @@ int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t
         Front f;
         f.n_or = n_or;
         f.clause_off_h = clause_off;
+        f.neg_h = neg;   // (validated, with at least one negation; nullptr: a plain DNF batch)
         front_host(g, n, nb, sc, ev, f);
         back_end(g, n, f, sc, ev, r.get(), prof, t0);
     }
@@ -2062,10 +2147,11 @@ int hgx_query_result_ms(const hgx_query_result* r, double* ms_total, double* ms_
 
 void hgx_query_result_free(hgx_query_result* r) { delete r; }
 
-int hgx_pattern_batch_dnf(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
-                          const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
-                          const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
-                          const int32_t* arity, hgx_query_result** out) {
+// hgx_pattern_batch_dnf, and hgx_pattern_batch_dnf_not with neg (the caller's program, not validated yet).
+static int dnf_entry(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
+                     const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
+                     const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
+                     const int32_t* arity, NotProgram* neg, hgx_query_result** out) {
     HGX_API_BEGIN
     if (!g || !out || n_queries < 0 || !clause_off) fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: bad argument");
     *out = nullptr;
@@ -2079,6 +2165,10 @@ int hgx_pattern_batch_dnf(hgx_graph* g, int32_t n_queries, const int64_t* clause
         fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: bad argument");
     if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch_dnf: not available on a partition shard");
     const int32_t n = (int32_t)nc;
+    if (neg) {
+        not_validate(g->A, n_queries, clause_off, *neg);
+        if (neg->n_negs == 0) neg = nullptr;
+    }
     NormBatch nb;
     nb.clause_off = clause_off;
     nb.n_or = n_queries;
@@ -2097,7 +2187,43 @@ int hgx_pattern_batch_dnf(hgx_graph* g, int32_t n_queries, const int64_t* clause
                   in.arity = arity[q];
               },
               nb);
-    return run_batch_dnf(g, n_queries, clause_off, n, nb, out);
+    return run_batch_dnf(g, n_queries, clause_off, n, nb, out, neg);
+    HGX_API_END
+}
+
+int hgx_pattern_batch_dnf(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
+                          const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
+                          const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
+                          const int32_t* arity, hgx_query_result** out) {
+    return dnf_entry(g, n_queries, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat, arity,
+                     nullptr, out);
+}
+
+int hgx_pattern_batch_dnf_not(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
+                              const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
+                              const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
+                              const int32_t* arity, const int64_t* neg_off, const int64_t* term_off,
+                              const int64_t* lit_off, const int32_t* lit, const int32_t* ops, int64_t n_ops,
+                              hgx_query_result** out) {
+    NotProgram p;
+    p.neg_off = neg_off;
+    p.term_off = term_off;
+    p.lit_off = lit_off;
+    p.lit = lit;
+    p.ops = ops;
+    p.n_ops = n_ops;
+    return dnf_entry(g, n_queries, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat, arity,
+                     neg_off ? &p : nullptr, out);
+}
+
+int hgx_query_result_not_stats(const hgx_query_result* r, int64_t* hits_tested, int64_t* hits_rejected, double* ms_not,
+                               double* bytes_not) {
+    HGX_API_BEGIN
+    if (!r) fail(HGX_E_INVALID, "hgx_query_result_not_stats: null result");
+    if (hits_tested) *hits_tested = r->hits_tested;
+    if (hits_rejected) *hits_rejected = r->hits_rejected;
+    if (ms_not) *ms_not = r->ms_not;
+    if (bytes_not) *bytes_not = r->bytes_not;
     HGX_API_END
 }
 

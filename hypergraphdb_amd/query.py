@@ -13,6 +13,9 @@ Reference (C = core/src/java/org/hypergraphdb):
   * hg.or: ExpressionBasedQuery.toDNF (ExpressionBasedQuery.java:94-167) turns any And / Or tree into an Or
     of Ands; OrToQuery (C/query/cond2qry/OrToQuery.java:14-43) chains UnionResults
     (C/query/impl/UnionResult.java).  Here: to_dnf + pattern_batch_dnf (one device call, include/hgx_dnf.h).
+  * hg.not: toDNF keeps a Not as an opaque leaf, AndToQuery.getQuery (C/query/cond2qry/AndToQuery.java:126-135,
+    :279-294) filters the clause's intersection with Not.satisfies (C/query/Not.java:33-36).  Here:
+    normalize_clause + lower_not + encode_negations, run by hgx_pattern_batch_dnf_not (include/hgx_not.h).
 """
 from __future__ import annotations
 
@@ -170,6 +173,33 @@ class Or(list):
         return "or(" + ", ".join(map(repr, self)) + ")"
 
 
+def _tree_key(c):
+    """A hashable, order-sensitive key of a condition tree: the reference's And / Or are lists and compare
+    element by element (And.java / Or.java extend ArrayList); And and Or never compare equal."""
+    if isinstance(c, And):
+        return ("and",) + tuple(_tree_key(x) for x in c)
+    if isinstance(c, Or):
+        return ("or",) + tuple(_tree_key(x) for x in c)
+    return c
+
+
+class Not:
+    """hg.not(pred) (C/query/Not.java): satisfies = !negated.satisfies (:33-36); Not(P) == Not(Q) iff P == Q
+    (:46-57), structurally and order-sensitively, so toDNF's HashSets dedupe it like any leaf."""
+
+    def __init__(self, negated):
+        self.negated = negated
+
+    def __eq__(self, o):
+        return isinstance(o, Not) and _tree_key(o.negated) == _tree_key(self.negated)
+
+    def __hash__(self):
+        return hash(("not", _tree_key(self.negated)))
+
+    def __repr__(self):
+        return f"not({self.negated!r})"
+
+
 class MapCondition:
     """hg.apply(mapping, cond)"""
 
@@ -243,6 +273,10 @@ class hg:
     @staticmethod
     def or_(*conds):
         return Or(conds)
+
+    @staticmethod
+    def not_(pred):
+        return Not(pred)
 
     @staticmethod
     def bfs(start, link_predicate=None, return_preceding=True, return_succeeding=True, reverse_order=False):
@@ -329,7 +363,10 @@ def to_dnf(cond) -> "Or":
     repeated inside the Or are dropped (the HashSets of :100 and :138).  A clause that normalize() reports
     as "empty" (it can match nothing) is dropped, as simplify removes Nothing from an Or.  A clause holding
     anything but the accelerated leaves raises HGXUnsupported, and so do more than MAX_DNF_CLAUSES clauses
-    (the distribution is exponential; the caller falls back to the CPU's OrToQuery)."""
+    (the distribution is exponential; the caller falls back to the CPU's OrToQuery).
+    A Not over a tree of the accelerated leaves is a leaf too: toDNF does not look inside it (no De Morgan
+    step), distributes and dedupes it like the others (Not.java:46-57); whether a clause is "empty" is
+    decided by its positive leaves alone."""
     def cap(clauses):
         if len(clauses) > MAX_DNF_CLAUSES:
             raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"more than {MAX_DNF_CLAUSES} clauses in the DNF of {cond!r}")
@@ -355,18 +392,168 @@ def to_dnf(cond) -> "Or":
             for sub in c:
                 acc = cap(dedupe(acc + dnf(sub)))
             return acc
-        if not isinstance(c, _LEAVES):
+        if isinstance(c, Not):
+            _nnf(c.negated, True)   # raises HGXUnsupported on anything but And / Or / Not over the leaves
+        elif not isinstance(c, _LEAVES):
             raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"shape not accelerated: {c!r}")
         return [(c,)]
 
-    return Or(And(cl) for cl in dnf(cond) if normalize(And(cl)) != "empty")
+    return Or(And(cl) for cl in dnf(cond)
+              if normalize(And([x for x in cl if not isinstance(x, Not)])) != "empty")
+
+
+# --- hg.not: the negations of a clause, lowered on the host (include/hgx_not.h) ---------------------------
+
+NOT_TYPE, NOT_INCIDENT, NOT_POSITIONED, NOT_ORDERED, NOT_LINK, NOT_ARITY = 1, 2, 3, 4, 5, 6
+
+
+def _nnf(p, pol):
+    """Negation normal form of ``p`` (``pol`` False: of its negation): nested Nots become the polarity of
+    the literals -- ("lit", leaf, polarity) under ("and", [...]) / ("or", [...])."""
+    if isinstance(p, Not):
+        return _nnf(p.negated, not pol)
+    if isinstance(p, (And, Or)):
+        conj = isinstance(p, And) == pol   # De Morgan: a negated And is an Or of the negated operands
+        return ("and" if conj else "or", [_nnf(c, pol) for c in p])
+    if isinstance(p, _LEAVES):
+        return ("lit", p, pol)
+    raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"shape not accelerated inside a Not: {p!r}")
+
+
+def lower_not(neg, max_terms=None):
+    """``neg`` = Not(P) -> the terms of P: its negation normal form in disjunctive normal form, a list of
+    tuples of (leaf, polarity) literals.  P holds iff every literal of some term does, so Not(P) holds iff
+    every term has a failing literal.  No term: P is false (an empty Or); an empty term: P is true (an empty
+    And).  More than ``max_terms`` (MAX_DNF_CLAUSES) terms raise HGXUnsupported."""
+    limit = MAX_DNF_CLAUSES if max_terms is None else max_terms
+
+    def cap(terms):
+        if len(terms) > limit:
+            raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"more than {limit} terms in the negations of {neg!r}")
+        return terms
+
+    def dedupe(terms):
+        seen, out = set(), []
+        for t in terms:
+            k = frozenset(t)
+            if k not in seen:
+                seen.add(k)
+                out.append(t)
+        return out
+
+    def terms(node):
+        if node[0] == "lit":
+            return [((node[1], node[2]),)]
+        if node[0] == "or":
+            acc = []
+            for sub in node[1]:
+                acc = cap(dedupe(acc + terms(sub)))
+            return acc
+        acc = [()]
+        for sub in node[1]:
+            acc = cap(dedupe([a + tuple(x for x in b if x not in a) for a in acc for b in terms(sub)]))
+        return acc
+
+    return terms(_nnf(neg.negated, True))
+
+
+def raw_satisfies(leaf, targets, type_) -> bool:
+    """The leaf's own satisfies() on a link with these targets and this type key -- what a Not negates, not
+    the leaf's query translation (the kinds of include/hgx_not.h; the kernel of hgx_not.hip restates them)."""
+    tg = [int(t) for t in targets]
+    if isinstance(leaf, AtomTypeCondition):          # AtomTypeCondition.java:121-135
+        return type_ == leaf.type
+    if isinstance(leaf, TypePlusCondition):          # TypePlusCondition.java:63-71
+        return type_ in leaf.types
+    if isinstance(leaf, IncidentCondition):          # IncidentCondition.java:63-76
+        return leaf.target in tg
+    if isinstance(leaf, PositionedIncidentCondition):   # PositionedIncidentCondition.java:123-177
+        n, (x, lb, ub, comp) = len(tg), leaf.record()
+        ub, lb = (ub + n if ub < 0 else ub), (lb + n if lb < 0 else lb)
+        if lb > ub or lb < 0 or ub < 0 or lb >= n or ub >= n:
+            return False
+        return any(t == x and ((lb <= i <= ub) != bool(comp)) for i, t in enumerate(tg))
+    if isinstance(leaf, OrderedLinkCondition):       # OrderedLinkCondition.java:92-124: [] satisfies every link
+        j = 0
+        for t in tg:
+            if j < len(leaf.targets) and leaf.targets[j] in (ANY, t):
+                j += 1
+        return j == len(leaf.targets)
+    if isinstance(leaf, LinkCondition):              # LinkCondition.java:101-140: positions counted, not members
+        members = set(leaf.targets)
+        return sum(t in members for t in tg) == len(members)
+    if isinstance(leaf, ArityCondition):             # ArityCondition.java:49-67
+        return len(tg) == leaf.arity
+    raise TypeError(leaf)
+
+
+def terms_hold(terms, targets, type_) -> bool:
+    """P of lower_not on one link: some term has every literal holding."""
+    return any(all(raw_satisfies(leaf, targets, type_) == pol for leaf, pol in term) for term in terms)
+
+
+def _literal(leaf):
+    """(kind, operands) of include/hgx_not.h"""
+    if isinstance(leaf, AtomTypeCondition):
+        return NOT_TYPE, [leaf.type]
+    if isinstance(leaf, TypePlusCondition):
+        return NOT_TYPE, sorted(leaf.types)
+    if isinstance(leaf, IncidentCondition):
+        return NOT_INCIDENT, [leaf.target]
+    if isinstance(leaf, PositionedIncidentCondition):
+        return NOT_POSITIONED, list(leaf.record())
+    if isinstance(leaf, OrderedLinkCondition):
+        return NOT_ORDERED, list(leaf.targets)
+    if isinstance(leaf, LinkCondition):
+        return NOT_LINK, list(dict.fromkeys(leaf.targets))   # the reference's target set: each member once
+    return NOT_ARITY, [leaf.arity]
+
+
+def normalize_clause(clause):
+    """One clause of to_dnf -> (normalize(And(its positive leaves)), [lower_not(n) for its Nots]).  The
+    terms of one clause are capped together at MAX_DNF_CLAUSES (HGXUnsupported beyond)."""
+    leaves = _flatten(clause if isinstance(clause, And) else And([clause]), [])
+    negs = [lower_not(c) for c in leaves if isinstance(c, Not)]
+    if sum(len(t) for t in negs) > MAX_DNF_CLAUSES:
+        raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"more than {MAX_DNF_CLAUSES} terms in the negations of {clause!r}")
+    return normalize(And([c for c in leaves if not isinstance(c, Not)])), negs
+
+
+def encode_negations(clause_negs):
+    """[per clause: [per negation: terms of lower_not]] -> (neg_off, term_off, lit_off, lit, ops) of
+    hgx_pattern_batch_dnf_not."""
+    neg_off, term_off, lit_off, lit, ops = [0], [0], [0], [], []
+    for negs in clause_negs:
+        for terms in negs:
+            for term in terms:
+                for leaf, pol in term:
+                    kind, operands = _literal(leaf)
+                    lit.extend((kind, int(bool(pol)), len(ops), len(ops) + len(operands)))
+                    ops.extend(operands)
+                lit_off.append(len(lit) // 4)
+            term_off.append(len(lit_off) - 1)
+        neg_off.append(len(term_off) - 1)
+    return (np.array(neg_off, np.int64), np.array(term_off, np.int64), np.array(lit_off, np.int64),
+            np.array(lit, np.int32), np.array(ops, np.int32))
+
+
+def decode_negations(neg_off, term_off, lit_off, lit, ops):
+    """The inverse of encode_negations up to the leaf classes: literals come back as
+    (kind, polarity, operand tuple)."""
+    return [[[tuple((int(lit[4 * l]), int(lit[4 * l + 1]), tuple(int(x) for x in ops[lit[4 * l + 2]:lit[4 * l + 3]]))
+                    for l in range(lit_off[t], lit_off[t + 1]))
+              for t in range(term_off[g], term_off[g + 1])]
+             for g in range(neg_off[c], neg_off[c + 1])]
+            for c in range(len(neg_off) - 1)]
 
 
 class QueryResult:
-    def __init__(self, offsets, ids, ms=None, union=None):
+    def __init__(self, offsets, ids, ms=None, union=None, negation=None):
         self.offsets, self.ids, self.ms = offsets, ids, ms
         # pattern_batch_dnf: {"clause_hits", "kept", "ms_union", "bytes_union"} (hgx_query_result_union_stats)
         self.union = union
+        # ... {"hits_tested", "hits_rejected", "ms_not", "bytes_not"} (hgx_query_result_not_stats)
+        self.negation = negation
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -513,27 +700,63 @@ def pattern_batch_dnf_arrays(snapshot, clause_off, type_off, types, inc_off, inc
     h = C.c_void_p()
     check(lib().hgx_pattern_batch_dnf(snapshot.handle, n, clause_off.ctypes.data, *(a.ctypes.data for a in arrs),
                                       C.byref(h)))
+    return _read_dnf_result(h, n)
+
+
+def _read_dnf_result(h, n) -> QueryResult:
     ch, kept, ms_u, by_u = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
     rc = lib().hgx_query_result_union_stats(h, C.byref(ch), C.byref(kept), C.byref(ms_u), C.byref(by_u))
+    te, rj, ms_n, by_n = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    rc2 = lib().hgx_query_result_not_stats(h, C.byref(te), C.byref(rj), C.byref(ms_n), C.byref(by_n))
     r = _read_result(h, n)   # frees the result
     check(rc)
+    check(rc2)
     r.union = {"clause_hits": ch.value, "kept": kept.value, "ms_union": ms_u.value, "bytes_union": by_u.value}
+    r.negation = {"hits_tested": te.value, "hits_rejected": rj.value, "ms_not": ms_n.value, "bytes_not": by_n.value}
     return r
+
+
+def pattern_batch_dnf_not_arrays(snapshot, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off,
+                                 pat, arity, neg_off, term_off, lit_off, lit, ops) -> QueryResult:
+    """Flat DNF batch with negations for hgx_pattern_batch_dnf_not (include/hgx_not.h): the arrays of
+    pattern_batch_dnf_arrays, then the negation program of encode_negations (all five None: no program)."""
+    clause_off = np.ascontiguousarray(clause_off, np.int64)
+    n = len(clause_off) - 1
+    if neg_off is None:
+        neg_off = term_off = lit_off = np.zeros(0, np.int64)
+        lit = ops = np.zeros(0, np.int32)
+    arrs = [np.ascontiguousarray(type_off, np.int64), np.ascontiguousarray(types, np.int32),
+            np.ascontiguousarray(inc_off, np.int64), np.ascontiguousarray(inc, np.int32),
+            np.ascontiguousarray(pos_off, np.int64), np.ascontiguousarray(pos, np.int32),
+            np.ascontiguousarray(pset_off, np.int64), np.ascontiguousarray(pat_off, np.int64),
+            np.ascontiguousarray(pat, np.int32), np.ascontiguousarray(arity, np.int32),
+            np.ascontiguousarray(neg_off, np.int64), np.ascontiguousarray(term_off, np.int64),
+            np.ascontiguousarray(lit_off, np.int64), np.ascontiguousarray(lit, np.int32),
+            np.ascontiguousarray(ops, np.int32)]
+    h = C.c_void_p()
+    check(lib().hgx_pattern_batch_dnf_not(snapshot.handle, n, clause_off.ctypes.data,
+                                          *(a.ctypes.data if a.size else None for a in arrs), len(arrs[-1]),
+                                          C.byref(h)))
+    return _read_dnf_result(h, n)
 
 
 def pattern_batch_dnf(snapshot, queries) -> QueryResult:
     """Evaluate many And / Or trees over the accelerated leaves in one device call: every query goes
     through to_dnf, its clauses run as one hgx_pattern_batch_ext-shaped batch and are united on the device
-    (ascending, each link atom once).  ``queries``: conditions, or lists of normalised clause dicts.
-    ``result.union`` holds the union statistics."""
-    clause_off, norm = [0], []
+    (ascending, each link atom once).  ``queries``: conditions, or lists of normalised clauses -- a dict, or
+    a (dict, negations) pair of normalize_clause.  A clause's Nots filter its hits on the device before the
+    union (hgx_pattern_batch_dnf_not); a batch without any goes through hgx_pattern_batch_dnf as before.
+    ``result.union`` / ``result.negation`` hold the statistics."""
+    clause_off, norm, negs = [0], [], []
     for q in queries:
-        if type(q) in (list, tuple):
-            norm.extend(q)
-        else:
-            norm.extend(normalize(c) for c in to_dnf(q))
+        for c in (q if type(q) in (list, tuple) else [normalize_clause(c) for c in to_dnf(q)]):
+            c, ng = c if type(c) is tuple else (c, [])
+            norm.append(c)
+            negs.append([] if c == "empty" else ng)   # (an "empty" clause runs as a NOP: nothing to filter)
         clause_off.append(len(norm))
-    return pattern_batch_dnf_arrays(snapshot, clause_off, *_ext_arrays(norm))
+    if not any(negs):
+        return pattern_batch_dnf_arrays(snapshot, clause_off, *_ext_arrays(norm))
+    return pattern_batch_dnf_not_arrays(snapshot, clause_off, *_ext_arrays(norm), *encode_negations(negs))
 
 
 def pattern_batch(snapshot, queries) -> QueryResult:
@@ -567,6 +790,8 @@ class GpuAndToQuery:
     """ConditionToQuery for And, registered with HGQueryConfiguration.addCompiler(And, ...)."""
 
     def getQuery(self, snapshot, cond):
+        if _has_not(cond):   # the Nots filter the And's hits on the device: one clause of the DNF path
+            return GpuOrToQuery().getQuery(snapshot, cond)
         norm = normalize(cond)
 
         class _Q:
@@ -576,6 +801,8 @@ class GpuAndToQuery:
         return _Q()
 
     def getMetaData(self, snapshot, cond):
+        if _has_not(cond):
+            return GpuOrToQuery().getMetaData(snapshot, cond)
         normalize(cond)
         return QueryMetaData(True, True, -1)
 
@@ -585,7 +812,7 @@ class GpuOrToQuery:
     HGQueryConfiguration.addCompiler(Or, ...): the condition's DNF as one device batch."""
 
     def getQuery(self, snapshot, cond):
-        clauses = [normalize(c) for c in to_dnf(cond)]
+        clauses = [normalize_clause(c) for c in to_dnf(cond)]
 
         class _Q:
             def execute(_self):
@@ -620,6 +847,10 @@ def _has_or(cond):
     return isinstance(cond, Or) or (isinstance(cond, And) and any(_has_or(c) for c in cond))
 
 
+def _has_not(cond):
+    return isinstance(cond, Not) or (isinstance(cond, (And, Or)) and any(_has_not(c) for c in cond))
+
+
 def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
     """hg.findAll(graph, cond) for the accelerated shapes."""
     if isinstance(cond, BFSCondition):
@@ -630,12 +861,14 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
         return seq.pairs(0)[1].tolist()
     if isinstance(cond, MapCondition):
         return sorted({v for v in (cond.mapping(x) for x in find_all(snapshot, cond.cond, config)) if v is not None})
-    if isinstance(cond, Or) or (isinstance(cond, And) and _has_or(cond)):
+    if isinstance(cond, Or) or (isinstance(cond, And) and _has_or(cond)) or _has_not(cond):
         compiler = (config.compiler(Or) if config else None) or GpuOrToQuery()
         try:
             return compiler.getQuery(snapshot, cond).execute()
         except HGXUnsupported:
-            pass   # a part the pattern engine does not take (Map / BFS sub-conditions): host set algebra
+            if _has_not(cond):
+                raise   # a Not over anything but the accelerated leaves, or without an anchor: the CPU's query
+            # a part the pattern engine does not take (Map / BFS sub-conditions): host set algebra
         if isinstance(cond, Or):
             return sorted(set().union(*(find_all(snapshot, c, config) for c in cond)))
         subs = _flatten(cond, [])
