@@ -5,7 +5,9 @@ This package is the host-side mirror of the reference interfaces on that path:
   snapshot.HyperGraphSnapshot   the store snapshot (bipartite CSR on the device)
   algorithms                    DefaultALGenerator / HGBreadthFirstTraversal / bfs_batch
   query                         hg.and/or/type/incident/orderedLink, GpuAndToQuery, GpuOrToQuery, pattern_batch,
-                                pattern_batch_dnf (include/hgx_dnf.h); hg.not_ on its clauses (include/hgx_not.h)
+                                pattern_batch_dnf (include/hgx_dnf.h); hg.not_ on its clauses (include/hgx_not.h);
+                                opt-in type-index scans of clauses without an anchor: pattern_batch_dnf(...,
+                                type_scan=True), GpuScanToQuery (include/hgx_scan.h)
   classics                      GraphClassics.dijkstra / shortest_paths (include/hgx_paths.h);
                                 hop_paths -> HopPaths, BfsResult.paths / depths / predecessors: unit-weight
                                 shortest paths read out of a batched BFS (include/hgx_hops.h)
@@ -15,7 +17,7 @@ from .algorithms import (AtomTypeCondition, BfsResult, DefaultALGenerator, HGBre
                          HopPaths, SequenceResult, bfs_sequence,
                          HGException, bfs_batch)
 from .classics import GraphClassics, LinkWeights, ShortestPathsResult, hop_paths, shortest_paths  # noqa: F401
-from .query import (And, ArityCondition, GpuAndToQuery, GpuOrToQuery, HGQueryConfiguration, LinkCondition,  # noqa: F401
+from .query import (And, ArityCondition, GpuAndToQuery, GpuOrToQuery, GpuScanToQuery, HGQueryConfiguration, LinkCondition,  # noqa: F401
                     Not, Or, PositionedIncidentCondition, TypePlusCondition, find_all, hg, pattern_batch,
                     pattern_batch_dnf, to_dnf)
 from .snapshot import HyperGraphSnapshot, export_store, rank_handles, read_snapshot, write_snapshot  # noqa: F401

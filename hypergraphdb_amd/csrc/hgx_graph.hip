@@ -39,7 +39,7 @@ void graph_release(hgx_graph* g) {
     HGX_FREE_OWN(link_atom); HGX_FREE_OWN(tgt_off); HGX_FREE_OWN(tgt_idx); HGX_FREE_OWN(link_type);
     HGX_FREE_OWN(inc_off); HGX_FREE_OWN(inc_row); HGX_FREE_OWN(inc_type); HGX_FREE_OWN(inc_ts_row);
     HGX_FREE_OWN(inc_ts_type); HGX_FREE_OWN(inc_ts_tgt); HGX_FREE_OWN(heavy_atom); HGX_FREE_OWN(chunks);
-    HGX_FREE_OWN(hasinc); HGX_FREE_OWN(inc_yf); HGX_FREE_OWN(pchunks);
+    HGX_FREE_OWN(hasinc); HGX_FREE_OWN(inc_yf); HGX_FREE_OWN(pchunks); HGX_FREE_OWN(type_idx);
 #undef HGX_FREE_OWN
     if (g->zacc) (void)hipFree(g->zacc);
     if (g->q_ticket) (void)hipFree(g->q_ticket);

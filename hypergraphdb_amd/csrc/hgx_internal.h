@@ -29,6 +29,7 @@
 #include "../../include/hgx_hops.h"
 #include "../../include/hgx_not.h"
 #include "../../include/hgx_paths.h"
+#include "../../include/hgx_scan.h"
 
 namespace hgx {
 
@@ -339,6 +340,14 @@ struct hgx_graph {
     // 32-byte record instead of two dependent random rows.
     int32_t* inc_ts_tgt = nullptr;
     bool q_inline = true;
+    // Type index of the links (hgx_scan.hip, built on the first scanned batch): one 16-byte record per link row,
+    // (link atom, arity, first target offset low / high word), the rows stably sorted by link_type -- so the
+    // links of one type are one segment, ascending by row and by atom.  type_key / type_seg: the sorted
+    // distinct type keys and their segment offsets, on the host (a context copies its snapshot's).
+    int4* type_idx = nullptr;
+    bool type_idx_built = false;
+    std::vector<int32_t> type_key;   // [n distinct types] ascending
+    std::vector<int64_t> type_seg;   // [n distinct types + 1]
 
     int64_t n_heavy = 0;            // heavy atoms (deg > kHeavyDegree)
     int64_t I_heavy = 0;            // incidence entries of heavy atoms
@@ -514,6 +523,57 @@ struct NotArgs {
 };
 // Enqueues the filter on s: no synchronisation, nothing read back by the host.
 void not_launch(const NotArgs& a, hipStream_t s);
+}  // namespace hgx
+
+namespace hgx {
+// The type index of g's links, built on first use (hgx_scan.hip; caller holds g->mu, g's device current).  A
+// context takes its snapshot's (built there under the snapshot's mutex).
+void ensure_type_index(hgx_graph* g);
+// hgx_graph_update: the links changed, the next scan rebuilds the index.
+void drop_type_index(hgx_graph* g);
+
+// One scanned clause of a DNF batch (hgx_pattern_batch_dnf_scan): a clause without an incidence anchor and
+// with exactly one type, evaluated over the type's segment of the index.
+struct ScanDesc {
+    int64_t seg_beg, seg_len;   // the type's segment of the index (seg_len 0: absent type or a NOP clause)
+    int64_t g0, g1;             // its negations in the program
+    int32_t clause;             // its index among the batch's clauses
+    int32_t type;               // its type key (a type literal of its negations compares with this)
+    int32_t arity;              // arity == k, or -1
+    int32_t min_arity;          // longest all-ANY ordered pattern (arity >= m)
+    int32_t needs_targets;      // a literal of its negations reads targets
+    int32_t pad;
+};
+// The scan stage of a DNF batch (hgx_scan.hip), between the clause stage (+ filter) and the
+// union: the hits of the scanned clauses, merged with the anchored clauses' runs into hits_out / run_out in
+// the layout the union reads.
+struct ScanArgs {
+    NotDev prog;
+    int32_t n_scan, n_clauses;
+    int64_t n_chunks;               // 64-entry chunks over every scanned clause (> 0)
+    const ScanDesc* desc;           // [n_scan]
+    const int64_t* chunk_beg;       // [n_scan + 1] first chunk of each scanned clause
+    const int64_t* clause_chunk;    // [n_clauses + 1] chunks of the scanned clauses before clause c
+    const int4* idx;                // the type index
+    const int32_t* tgt_idx;
+    u64* word;                      // [n_chunks] keep bits of the chunk's lanes
+    int64_t* cnt;                   // [n_chunks + 1] their population counts (last: 0)
+    int64_t* cpre;                  // [n_chunks + 1] exclusive prefix sum of cnt
+    void* tmp;                      // scan temporary storage (scan_temp_bytes)
+    size_t tmp_bytes;
+    int64_t* stat;                  // [8] statistics of the clause stage: [1] needed capacity, [2] overflow
+    const int64_t* run_in;          // [n_clauses + 1] hit offsets of the clause stage (scanned clauses: empty runs)
+    const int32_t* hits_in;         // [cap] its hits
+    int64_t cap;
+    bool move;                      // the batch has an anchored clause: its hits move to their merged places
+    int64_t* run_out;               // [n_clauses + 1] merged hit offsets
+    int32_t* hits_out;              // [cap] merged hits, each clause ascending
+    unsigned long long* ctr;        // [8] rows kept, targets read, rows that walked a program
+    unsigned long long* out_ctr;    // [8] mapped: ctr
+};
+size_t scan_temp_bytes(int64_t n_chunks, hipStream_t s);
+// Enqueues the scan stage on s: no synchronisation, nothing read back by the host.
+void scan_launch(const ScanArgs& a, hipStream_t s);
 }  // namespace hgx
 
 // One batch (<= 1024 seeds) of a batched BFS and the result object of hgx_bfs_batch (hgx_bfs.hip makes and

@@ -1072,6 +1072,9 @@ struct hgx_query_result {
     // hgx_pattern_batch_dnf_not: clause hits the filter tested / rejected, device ms and algorithmic bytes of it
     int64_t hits_tested = 0, hits_rejected = 0;
     double ms_not = 0, bytes_not = 0;
+    // hgx_pattern_batch_dnf_scan: scanned clauses, index rows they covered / kept, device ms and algorithmic bytes
+    int64_t clauses_scanned = 0, rows_scanned = 0, rows_kept = 0;
+    double ms_scan = 0, bytes_scan = 0;
 };
 
 // A packed batch resident in device memory (hgx_query_set_create), in the staging layout of the
@@ -1116,6 +1119,24 @@ struct NormBatch {
     // and an error names the Or query and the clause inside it
     const int64_t* clause_off = nullptr;
     int32_t n_or = 0;
+    // hgx_pattern_batch_dnf_scan: a clause without an anchor and with exactly one type is no error; it enters
+    // the clause stage as a NOP and is listed here for the scan stage (hgx_scan.hip)
+    bool allow_scan = false;
+    struct ScanClause {
+        int32_t clause, type, arity, min_arity, nop;
+    };
+    std::vector<ScanClause> scan;
+};
+
+// The scan stage's part of one batch, planned on the host from the type histogram (plan_scan).
+struct ScanPlan {
+    std::vector<ScanDesc> desc;           // the scanned clauses that own chunks (no NOP, type present)
+    std::vector<int64_t> chunk_beg;       // [desc + 1]
+    std::vector<int64_t> clause_chunk;    // [n clauses + 1]
+    int64_t n_chunks = 0, rows = 0;
+    int32_t clauses = 0;                  // every scanned clause
+    bool anchored = false;                // the batch has an anchored clause
+    bool anchored_negs = false;           //   ... one with a negation (the filter stage runs)
 };
 
 template <class Get>
@@ -1186,6 +1207,20 @@ void normalise(hgx_graph* g, int32_t n, Get get, NormBatch& nb) {
         }
         d.r_end = (int64_t)nb.p_off.size() - 1;
         d.a_end = (int64_t)nb.anchors.size();
+        if (d.a_end == d.a_beg && nb.allow_scan) {
+            if (d.t_end == d.t_beg)
+                fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch_dnf_scan: query " + qs() +
+                                            " has neither an incidence anchor nor a type (nothing to scan)");
+            if (d.t_end - d.t_beg > 1)
+                fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch_dnf_scan: query " + qs() +
+                                            " has no incidence anchor and more than one type (one clause per type)");
+            int32_t min_arity = 0;   // every pattern is all-ANY here (a target would be an anchor)
+            for (int64_t r = d.r_beg; r < d.r_end; ++r)
+                min_arity = std::max(min_arity, (int32_t)(nb.p_off[r + 1] - nb.p_off[r]));
+            nb.scan.push_back({q, nb.types[d.t_beg], d.arity, min_arity, nb.nop[q]});
+            nb.nop[q] = 1;   // the clause stage leaves it an empty run
+            continue;
+        }
         if (d.a_end == d.a_beg)
             fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch: query " + qs() + " has no incidence anchor");
         if (d.a_end - d.a_beg > kMaxAnchors) fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch: too many anchors");
@@ -1373,6 +1408,11 @@ struct Front {
     // ... with negations (hgx_pattern_batch_dnf_not): the validated program goes up with the conditions too
     const NotProgram* neg_h = nullptr;
     NotDev neg;                            //   its device copy
+    // ... with scanned clauses (hgx_pattern_batch_dnf_scan): the plan goes up with the conditions as well
+    const ScanPlan* scan = nullptr;
+    const ScanDesc* scan_desc = nullptr;   //   device copies
+    const int64_t* scan_chunk_beg = nullptr;
+    const int64_t* scan_clause_chunk = nullptr;
 };
 
 // Buffers taken from the graph pool for one call, released on every exit path.
@@ -1394,6 +1434,7 @@ struct Events {
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t u = nullptr;   // start of the union stage (DNF batches only: taken on first use)
     hipEvent_t nt = nullptr;  // start of the negation filter (DNF batches with negations only)
+    hipEvent_t sn = nullptr;  // start of the scan stage (DNF batches with scanned clauses only)
     bool on = false;
     void init(hgx_graph* gg) {
         g = gg;
@@ -1423,11 +1464,13 @@ struct Events {
     }
     void rec_union(hipStream_t s) { rec_extra(u, s); }
     void rec_not(hipStream_t s) { rec_extra(nt, s); }
+    void rec_scan(hipStream_t s) { rec_extra(sn, s); }
     ~Events() {
         for (int i = 0; i < 4; ++i)
             if (e[i]) g->ev_pool.push_back(e[i]);
         if (u) g->ev_pool.push_back(u);
         if (nt) g->ev_pool.push_back(nt);
+        if (sn) g->ev_pool.push_back(sn);
     }
 };
 
@@ -1462,6 +1505,9 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
         o_nr = u.take(sizeof(int32_t) * 4 * (size_t)np->n_lits);
         o_no = u.take(sizeof(int32_t) * (size_t)np->n_ops);
     }
+    const ScanPlan* sp = f.scan && f.scan->n_chunks > 0 ? f.scan : nullptr;
+    const size_t o_sd = sp ? u.take(bytes_of(sp->desc)) : 0, o_sb = sp ? u.take(bytes_of(sp->chunk_beg)) : 0,
+                 o_sc = sp ? u.take(bytes_of(sp->clause_chunk)) : 0;
     char* h = (char*)g->pinned_buf(u.off);
     auto put = [&](size_t o, const auto& v) {
         if (!v.empty()) std::memcpy(h + o, v.data(), sizeof(v[0]) * v.size());
@@ -1473,6 +1519,11 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     put(o_poff, nb.p_off);
     put(o_pat, nb.pattern);
     put(o_nop, nb.nop);
+    if (sp) {
+        put(o_sd, sp->desc);
+        put(o_sb, sp->chunk_beg);
+        put(o_sc, sp->clause_chunk);
+    }
     if (f.n_or >= 0) std::memcpy(h + o_cl, f.clause_off_h, sizeof(int64_t) * ((size_t)f.n_or + 1));
     if (np) {
         const int64_t zero = 0;   // (a program without terms has no lit_off)
@@ -1501,6 +1552,11 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
         f.neg.lit_off = (const int64_t*)(d + o_nl);
         f.neg.lit = (const int4*)(d + o_nr);
         f.neg.ops = (const int32_t*)(d + o_no);
+    }
+    if (sp) {
+        f.scan_desc = (const ScanDesc*)(d + o_sd);
+        f.scan_chunk_beg = (const int64_t*)(d + o_sb);
+        f.scan_clause_chunk = (const int64_t*)(d + o_sc);
     }
     f.cond_bytes = 20.0 * nb.anchors.size() + 4.0 * nb.types.size() + 4.0 * nb.pos.size() +
                    4.0 * nb.pattern.size() + (double)sizeof(QDesc) * n;
@@ -1631,8 +1687,13 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         // after the match's; with negations ctr[20], the filter's eight after those)
         const bool dnf = f.n_or >= 0;
         const int32_t nq = dnf ? f.n_or : n;   // queries of the result (a DNF batch: n counts its clauses)
-        const bool neg = dnf && f.neg.neg_off;   // ... with negations: the filter's eight counters after the union's
-        const size_t m_stat = 0, m_ctr = 64, m_nctr = 160, m_qoff = dnf ? (neg ? 224 : 160) : 128;
+        // ... with negations: the filter's eight counters after the union's (a batch with scanned clauses runs the
+        // filter only when an anchored clause has a negation: the scan tests its own rows)
+        const bool neg = dnf && f.neg.neg_off && (!f.scan || f.scan->anchored_negs);
+        // ... with scanned clauses: the scan's eight counters after the filter's
+        const bool scan = dnf && f.scan && f.scan->n_chunks > 0;
+        const size_t m_stat = 0, m_ctr = 64, m_nctr = 160, m_sctr = 224,
+                     m_qoff = dnf ? (f.scan ? 288 : neg ? 224 : 160) : 128;
         const size_t m_ids = m_qoff + ((8 * (size_t)(nq + 1) + 15) & ~(size_t)15);
         char* hm = (char*)g->mapped_buf(m_ids + 4 * (size_t)capK);
         void* hmd = nullptr;
@@ -1691,6 +1752,37 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             na.out_ctr = (u64*)(rd + m_nctr);
             un.run_off = na.run_out;
             un.hits = na.hits_out;
+        }
+        // scanned clauses: the scan stage merges its hits with the runs the clause stage (and the filter) left
+        // and the union reads the merged space (hgx_scan.hip)
+        ScanArgs sa{};
+        if (scan) {
+            const ScanPlan& sp = *f.scan;
+            sa.prog = f.neg;
+            sa.n_scan = (int32_t)sp.desc.size();
+            sa.n_clauses = n;
+            sa.n_chunks = sp.n_chunks;
+            sa.desc = f.scan_desc;
+            sa.chunk_beg = f.scan_chunk_beg;
+            sa.clause_chunk = f.scan_clause_chunk;
+            sa.idx = g->type_idx;
+            sa.tgt_idx = g->tgt_idx;
+            sa.word = (u64*)w.take(sizeof(u64) * (size_t)sp.n_chunks);
+            sa.cnt = (int64_t*)w.take(sizeof(int64_t) * ((size_t)sp.n_chunks + 1));
+            sa.cpre = (int64_t*)w.take(sizeof(int64_t) * ((size_t)sp.n_chunks + 1));
+            sa.tmp_bytes = scan_temp_bytes(sp.n_chunks, s);
+            sa.tmp = w.take(sa.tmp_bytes);
+            sa.stat = stat_d;
+            sa.run_in = un.run_off;
+            sa.hits_in = un.hits;
+            sa.cap = capK;
+            sa.move = sp.anchored;
+            sa.run_out = (int64_t*)w.take(sizeof(int64_t) * ((size_t)n + 1));
+            sa.hits_out = (int32_t*)w.take(sizeof(int32_t) * (size_t)capK);
+            sa.ctr = (u64*)w.take(sizeof(u64) * 8);
+            sa.out_ctr = (u64*)(rd + m_sctr);
+            un.run_off = sa.run_out;
+            un.hits = sa.hits_out;
         }
         const int64_t nbp = std::max<int64_t>(1, ceil_div(capC, kPlaceChunks));
         // derived flat index: no scan launch between the front kernel and the match (its counter shards
@@ -1752,6 +1844,10 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             ev.rec_not(s);
             not_launch(na, s);
         }
+        if (scan) {
+            ev.rec_scan(s);
+            scan_launch(sa, s);
+        }
         if (dnf) {
             ev.rec_union(s);
             union_launch(un, s);
@@ -1810,6 +1906,34 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
                 r->ms_union = c;
             }
         }
+        int64_t scan_kept = 0;
+        if (f.scan && dnf) {
+            // algorithmic bytes of the scan stage: per index row its 16-byte record; 4 B per
+            // target read; per chunk its keep word and count written, the count read and its prefix written by
+            // the scan, word and prefix read by the emit (48 B); per row kept the atom read again and the id
+            // written (8 B); per anchored hit moved its id read and written; per scanned clause its descriptor
+            // read by both kernels and its first chunk; per clause the four offsets of the merge; the program once
+            const ScanPlan& sp = *f.scan;
+            r->clauses_scanned = sp.clauses;
+            r->rows_scanned = sp.rows;
+            if (scan) {
+                const u64* sc_h = (const u64*)(hm + m_sctr);
+                scan_kept = (int64_t)sc_h[0];
+                r->rows_kept = scan_kept;
+                double prog = 0;
+                if (f.neg_h && sc_h[2])
+                    prog = 8.0 * ((double)f.neg_h->n_negs + 1 + (double)f.neg_h->n_terms + 1) + 16.0 * (double)f.neg_h->n_lits +
+                           4.0 * (double)f.neg_h->n_ops;
+                r->bytes_scan = 16.0 * (double)sp.rows + 4.0 * (double)sc_h[1] + 48.0 * (double)sp.n_chunks +
+                                8.0 * (double)scan_kept + (sp.anchored ? 8.0 * (double)(stat[6] - scan_kept) : 0.0) +
+                                (2.0 * sizeof(ScanDesc) + 8.0) * (double)sp.desc.size() + 32.0 * ((double)n + 1) + prog;
+                if (ev.on) {
+                    float c = 0;
+                    HGX_HIP(hipEventElapsedTime(&c, ev.sn, ev.u));
+                    r->ms_scan = c;
+                }
+            }
+        }
         if (neg) {
             // algorithmic bytes of the filter: per clause hit its id read and its flag written,
             // read by the scan and by the compaction, and its 8-byte prefix; per tested hit the offset pair,
@@ -1817,15 +1941,16 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             // program once; the run offsets read and written
             const u64* nc = (const u64*)(hm + m_nctr);
             const NotProgram& np = *f.neg_h;
-            const double H0 = (double)stat[6] + (double)nc[1];   // hits before the filter
+            const double H1 = (double)(stat[6] - scan_kept);     // anchored hits after the filter
+            const double H0 = H1 + (double)nc[1];                // ... and before it
             r->hits_tested = (int64_t)nc[0];
             r->hits_rejected = (int64_t)nc[1];
             r->bytes_not = 15.0 * H0 + 16.0 * (double)nc[0] + 4.0 * ((double)nc[2] + (double)nc[3] + (double)nc[4]) +
-                           4.0 * (double)stat[6] + 8.0 * ((double)n + 1 + (double)np.n_negs + 1 + (double)np.n_terms + 1) +
+                           4.0 * H1 + 8.0 * ((double)n + 1 + (double)np.n_negs + 1 + (double)np.n_terms + 1) +
                            16.0 * (double)np.n_lits + 4.0 * (double)np.n_ops + 16.0 * ((double)n + 1);
             if (ev.on) {
                 float c = 0;
-                HGX_HIP(hipEventElapsedTime(&c, ev.nt, ev.u));
+                HGX_HIP(hipEventElapsedTime(&c, ev.nt, scan ? ev.sn : ev.u));
                 r->ms_not = c;
             }
         }
@@ -1896,6 +2021,51 @@ int run_batch(hgx_graph* g, int32_t n, NormBatch& nb, hgx_query_result** out) {
 // A DNF batch: the n clauses of nb run through the same front and back end, whose placement leaves the
 // clause hits in device memory; the union stage (hgx_union.hip) writes the n_or results.  Takes the graph
 // mutex itself, like run_batch_with (no cross-thread coalescing).
+// The scanned clauses of nb as the scan stage's plan: their segments from the type histogram (built on first
+// use; caller holds g->mu), cut into 64-entry chunks.
+void plan_scan(hgx_graph* g, int32_t n, const NormBatch& nb, const NotProgram* neg, ScanPlan& sp) {
+    ensure_type_index(g);
+    sp.clauses = (int32_t)nb.scan.size();
+    sp.clause_chunk.assign((size_t)n + 1, 0);
+    sp.chunk_beg.assign(1, 0);
+    size_t k = 0;
+    for (int32_t c = 0; c < n; ++c) {
+        sp.clause_chunk[c] = sp.n_chunks;
+        const bool scanned = k < nb.scan.size() && nb.scan[k].clause == c;
+        const int64_t g0 = neg ? neg->neg_off[c] : 0, g1 = neg ? neg->neg_off[c + 1] : 0;
+        if (!scanned) {
+            sp.anchored = true;
+            if (g1 > g0) sp.anchored_negs = true;
+            continue;
+        }
+        const NormBatch::ScanClause& sc = nb.scan[k++];
+        if (sc.nop) continue;
+        const auto it = std::lower_bound(g->type_key.begin(), g->type_key.end(), sc.type);
+        if (it == g->type_key.end() || *it != sc.type) continue;
+        const size_t ti = (size_t)(it - g->type_key.begin());
+        ScanDesc d{};
+        d.seg_beg = g->type_seg[ti];
+        d.seg_len = g->type_seg[ti + 1] - d.seg_beg;
+        d.g0 = g0;
+        d.g1 = g1;
+        d.clause = c;
+        d.type = sc.type;
+        d.arity = sc.arity;
+        d.min_arity = sc.min_arity;
+        for (int64_t gg = g0; gg < g1 && !d.needs_targets; ++gg)
+            for (int64_t t = neg->term_off[gg]; t < neg->term_off[gg + 1] && !d.needs_targets; ++t)
+                for (int64_t l = neg->lit_off[t]; l < neg->lit_off[t + 1]; ++l) {
+                    const int32_t kind = neg->lit[4 * l];
+                    if (kind != HGX_NOT_TYPE && kind != HGX_NOT_ARITY) d.needs_targets = 1;
+                }
+        sp.rows += d.seg_len;
+        sp.n_chunks += ceil_div(d.seg_len, 64);
+        sp.desc.push_back(d);
+        sp.chunk_beg.push_back(sp.n_chunks);
+    }
+    sp.clause_chunk[n] = sp.n_chunks;
+}
+
 int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t n, NormBatch& nb,
                   hgx_query_result** out, const NotProgram* neg = nullptr) {
     HGX_API_BEGIN
@@ -1916,6 +2086,11 @@ int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t
         f.n_or = n_or;
         f.clause_off_h = clause_off;
         f.neg_h = neg;   // (validated, with at least one negation; nullptr: a plain DNF batch)
+        ScanPlan sp;
+        if (!nb.scan.empty()) {   // (hgx_pattern_batch_dnf_scan only; none: exactly hgx_pattern_batch_dnf_not)
+            plan_scan(g, n, nb, neg, sp);
+            f.scan = &sp;
+        }
         front_host(g, n, nb, sc, ev, f);
         back_end(g, n, f, sc, ev, r.get(), prof, t0);
     }
@@ -2151,7 +2326,7 @@ void hgx_query_result_free(hgx_query_result* r) { delete r; }
 static int dnf_entry(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
                      const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
                      const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
-                     const int32_t* arity, NotProgram* neg, hgx_query_result** out) {
+                     const int32_t* arity, NotProgram* neg, hgx_query_result** out, bool scan = false) {
     HGX_API_BEGIN
     if (!g || !out || n_queries < 0 || !clause_off) fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: bad argument");
     *out = nullptr;
@@ -2172,6 +2347,7 @@ static int dnf_entry(hgx_graph* g, int32_t n_queries, const int64_t* clause_off,
     NormBatch nb;
     nb.clause_off = clause_off;
     nb.n_or = n_queries;
+    nb.allow_scan = scan;
     normalise(g, n,
               [&](int32_t q, QueryIn& in) {
                   in.n_types = (int32_t)(type_off[q + 1] - type_off[q]);
@@ -2214,6 +2390,35 @@ int hgx_pattern_batch_dnf_not(hgx_graph* g, int32_t n_queries, const int64_t* cl
     p.n_ops = n_ops;
     return dnf_entry(g, n_queries, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat, arity,
                      neg_off ? &p : nullptr, out);
+}
+
+int hgx_pattern_batch_dnf_scan(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
+                               const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
+                               const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
+                               const int32_t* arity, const int64_t* neg_off, const int64_t* term_off,
+                               const int64_t* lit_off, const int32_t* lit, const int32_t* ops, int64_t n_ops,
+                               hgx_query_result** out) {
+    NotProgram p;
+    p.neg_off = neg_off;
+    p.term_off = term_off;
+    p.lit_off = lit_off;
+    p.lit = lit;
+    p.ops = ops;
+    p.n_ops = n_ops;
+    return dnf_entry(g, n_queries, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat, arity,
+                     neg_off ? &p : nullptr, out, true);
+}
+
+int hgx_query_result_scan_stats(const hgx_query_result* r, int64_t* clauses_scanned, int64_t* rows_scanned,
+                                int64_t* rows_kept, double* ms_scan, double* bytes_scan) {
+    HGX_API_BEGIN
+    if (!r) fail(HGX_E_INVALID, "hgx_query_result_scan_stats: null result");
+    if (clauses_scanned) *clauses_scanned = r->clauses_scanned;
+    if (rows_scanned) *rows_scanned = r->rows_scanned;
+    if (rows_kept) *rows_kept = r->rows_kept;
+    if (ms_scan) *ms_scan = r->ms_scan;
+    if (bytes_scan) *bytes_scan = r->bytes_scan;
+    HGX_API_END
 }
 
 int hgx_query_result_not_stats(const hgx_query_result* r, int64_t* hits_tested, int64_t* hits_rejected, double* ms_not,

@@ -16,6 +16,13 @@ Reference (C = core/src/java/org/hypergraphdb):
   * hg.not: toDNF keeps a Not as an opaque leaf, AndToQuery.getQuery (C/query/cond2qry/AndToQuery.java:126-135,
     :279-294) filters the clause's intersection with Not.satisfies (C/query/Not.java:33-36).  Here:
     normalize_clause + lower_not + encode_negations, run by hgx_pattern_batch_dnf_not (include/hgx_not.h).
+  * A clause without an incidence anchor: AndToQuery.getQuery (AndToQuery.java:120-294) scans indexByType.find(T)
+    and filters the scan with the remaining conditions.  Here, opt-in only: pattern_batch_dnf(..., type_scan=True)
+    / GpuScanToQuery split such a clause into one clause per type (split_type_scan) and run the batch through
+    hgx_pattern_batch_dnf_scan (include/hgx_scan.h), which scans the device type index.  THE SNAPSHOT KNOWS THE
+    TYPES OF LINK ATOMS ONLY: a scanned clause delivers the LINK atoms of the type that pass its predicates;
+    indexByType.find(T) also returns node atoms of type T.  The two agree whenever T has no node instances --
+    the caller opts in knowing that, and nothing routes a clause to the scan by default.
 """
 from __future__ import annotations
 
@@ -548,8 +555,11 @@ def decode_negations(neg_off, term_off, lit_off, lit, ops):
 
 
 class QueryResult:
-    def __init__(self, offsets, ids, ms=None, union=None, negation=None):
+    def __init__(self, offsets, ids, ms=None, union=None, negation=None, scan=None):
         self.offsets, self.ids, self.ms = offsets, ids, ms
+        # pattern_batch_dnf(type_scan=True): {"clauses_scanned", "rows_scanned", "rows_kept", "ms_scan",
+        # "bytes_scan"} (hgx_query_result_scan_stats)
+        self.scan = scan
         # pattern_batch_dnf: {"clause_hits", "kept", "ms_union", "bytes_union"} (hgx_query_result_union_stats)
         self.union = union
         # ... {"hits_tested", "hits_rejected", "ms_not", "bytes_not"} (hgx_query_result_not_stats)
@@ -703,14 +713,21 @@ def pattern_batch_dnf_arrays(snapshot, clause_off, type_off, types, inc_off, inc
     return _read_dnf_result(h, n)
 
 
-def _read_dnf_result(h, n) -> QueryResult:
+def _read_dnf_result(h, n, scan=False) -> QueryResult:
     ch, kept, ms_u, by_u = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
     rc = lib().hgx_query_result_union_stats(h, C.byref(ch), C.byref(kept), C.byref(ms_u), C.byref(by_u))
     te, rj, ms_n, by_n = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
     rc2 = lib().hgx_query_result_not_stats(h, C.byref(te), C.byref(rj), C.byref(ms_n), C.byref(by_n))
+    cs, rs, rk, ms_s, by_s = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    rc3 = lib().hgx_query_result_scan_stats(h, C.byref(cs), C.byref(rs), C.byref(rk), C.byref(ms_s),
+                                            C.byref(by_s)) if scan else _lib.HGX_OK
     r = _read_result(h, n)   # frees the result
     check(rc)
     check(rc2)
+    check(rc3)
+    if scan:
+        r.scan = {"clauses_scanned": cs.value, "rows_scanned": rs.value, "rows_kept": rk.value, "ms_scan": ms_s.value,
+                  "bytes_scan": by_s.value}
     r.union = {"clause_hits": ch.value, "kept": kept.value, "ms_union": ms_u.value, "bytes_union": by_u.value}
     r.negation = {"hits_tested": te.value, "hits_rejected": rj.value, "ms_not": ms_n.value, "bytes_not": by_n.value}
     return r
@@ -740,20 +757,73 @@ def pattern_batch_dnf_not_arrays(snapshot, clause_off, type_off, types, inc_off,
     return _read_dnf_result(h, n)
 
 
-def pattern_batch_dnf(snapshot, queries) -> QueryResult:
+def pattern_batch_dnf_scan_arrays(snapshot, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off,
+                                  pat, arity, neg_off=None, term_off=None, lit_off=None, lit=None,
+                                  ops=None) -> QueryResult:
+    """Flat DNF batch for hgx_pattern_batch_dnf_scan (include/hgx_scan.h): the arrays of
+    pattern_batch_dnf_not_arrays; a clause without an incidence anchor and with exactly one type is scanned
+    over the type index (its LINK atoms of that type).  ``result.scan`` holds the scan statistics."""
+    clause_off = np.ascontiguousarray(clause_off, np.int64)
+    n = len(clause_off) - 1
+    if neg_off is None:
+        neg_off = term_off = lit_off = np.zeros(0, np.int64)
+        lit = ops = np.zeros(0, np.int32)
+    arrs = [np.ascontiguousarray(type_off, np.int64), np.ascontiguousarray(types, np.int32),
+            np.ascontiguousarray(inc_off, np.int64), np.ascontiguousarray(inc, np.int32),
+            np.ascontiguousarray(pos_off, np.int64), np.ascontiguousarray(pos, np.int32),
+            np.ascontiguousarray(pset_off, np.int64), np.ascontiguousarray(pat_off, np.int64),
+            np.ascontiguousarray(pat, np.int32), np.ascontiguousarray(arity, np.int32),
+            np.ascontiguousarray(neg_off, np.int64), np.ascontiguousarray(term_off, np.int64),
+            np.ascontiguousarray(lit_off, np.int64), np.ascontiguousarray(lit, np.int32),
+            np.ascontiguousarray(ops, np.int32)]
+    h = C.c_void_p()
+    check(lib().hgx_pattern_batch_dnf_scan(snapshot.handle, n, clause_off.ctypes.data,
+                                           *(a.ctypes.data if a.size else None for a in arrs), len(arrs[-1]),
+                                           C.byref(h)))
+    return _read_dnf_result(h, n, scan=True)
+
+
+def is_anchored(norm) -> bool:
+    """A normalised clause has an incidence anchor: an incident target, a positioned target or a non-ANY
+    pattern target (ExpressionBasedQuery.expand adds incident(x) for it)."""
+    return bool(norm["inc"] or norm["pos"] or any(t != ANY for p in norm["patterns"] for t in p))
+
+
+def split_type_scan(norm, negs):
+    """One normalised clause of normalize_clause -> the clauses hgx_pattern_batch_dnf_scan takes for it.  A
+    clause without an anchor and with k >= 1 types becomes k one-type clauses with the negations repeated:
+    expand turns a TypePlusCondition into an Or of AtomTypeConditions (ExpressionBasedQuery.java:606-627) and
+    toDNF distributes it.  An anchored clause, an "empty" one and a clause with neither anchor nor type (the
+    engine refuses that one: nothing to scan) pass through untouched."""
+    if norm == "empty" or is_anchored(norm) or len(norm["types"]) <= 1:
+        return [(norm, negs)]
+    return [(dict(norm, types=[t]), negs) for t in norm["types"]]
+
+
+def pattern_batch_dnf(snapshot, queries, type_scan=False) -> QueryResult:
     """Evaluate many And / Or trees over the accelerated leaves in one device call: every query goes
     through to_dnf, its clauses run as one hgx_pattern_batch_ext-shaped batch and are united on the device
     (ascending, each link atom once).  ``queries``: conditions, or lists of normalised clauses -- a dict, or
     a (dict, negations) pair of normalize_clause.  A clause's Nots filter its hits on the device before the
     union (hgx_pattern_batch_dnf_not); a batch without any goes through hgx_pattern_batch_dnf as before.
-    ``result.union`` / ``result.negation`` hold the statistics."""
+    ``result.union`` / ``result.negation`` hold the statistics.
+    ``type_scan=True`` (off by default: without it a clause without an incidence anchor raises HGXUnsupported, as
+    ever) also takes clauses without an anchor that have a type: each is split into one clause per type
+    (split_type_scan) and the batch runs through hgx_pattern_batch_dnf_scan, which scans the type index.  Such a
+    clause delivers the LINK atoms of its type that pass -- the snapshot holds no node types, so it equals the
+    reference's indexByType scan only for a type whose instances are all links.  ``result.scan`` holds the scan
+    statistics."""
     clause_off, norm, negs = [0], [], []
     for q in queries:
         for c in (q if type(q) in (list, tuple) else [normalize_clause(c) for c in to_dnf(q)]):
             c, ng = c if type(c) is tuple else (c, [])
-            norm.append(c)
-            negs.append([] if c == "empty" else ng)   # (an "empty" clause runs as a NOP: nothing to filter)
+            for c1, ng1 in (split_type_scan(c, ng) if type_scan else [(c, ng)]):
+                norm.append(c1)
+                negs.append([] if c1 == "empty" else ng1)   # (an "empty" clause runs as a NOP: nothing to filter)
         clause_off.append(len(norm))
+    if type_scan:
+        return pattern_batch_dnf_scan_arrays(snapshot, clause_off, *_ext_arrays(norm),
+                                             *(encode_negations(negs) if any(negs) else ()))
     if not any(negs):
         return pattern_batch_dnf_arrays(snapshot, clause_off, *_ext_arrays(norm))
     return pattern_batch_dnf_not_arrays(snapshot, clause_off, *_ext_arrays(norm), *encode_negations(negs))
@@ -823,6 +893,32 @@ class GpuOrToQuery:
     def getMetaData(self, snapshot, cond):
         """OrToQuery.getMetaData (OrToQuery.java:44-76): ordered and random-access when every operand
         is -- every accelerated clause is (GpuAndToQuery.getMetaData)."""
+        try:
+            to_dnf(cond)
+        except HGXUnsupported:
+            return QueryMetaData(False, False, -1)
+        return QueryMetaData(True, True, -1)
+
+
+class GpuScanToQuery:
+    """ConditionToQuery for And and Or that also takes clauses without an incidence anchor, by a scan of the
+    device type index (include/hgx_scan.h).  Opt-in: a caller registers it with
+    HGQueryConfiguration.addCompiler(And, GpuScanToQuery()) and (Or, ...) for a graph whose scanned types have
+    link instances only -- a scanned clause delivers the LINK atoms of its type, the reference's indexByType
+    scan also the nodes of that type.  Without it find_all keeps refusing such a clause."""
+
+    def getQuery(self, snapshot, cond):
+        clauses = [normalize_clause(c) for c in to_dnf(cond)]
+
+        class _Q:
+            def execute(_self):
+                return list(pattern_batch_dnf(snapshot, [clauses], type_scan=True)[0].tolist())
+
+        return _Q()
+
+    def getMetaData(self, snapshot, cond):
+        """Ordered and random-access: every clause's run ascends and the union keeps the order (AndToQuery
+        over one ordered set, OrToQuery.java:44-76)."""
         try:
             to_dnf(cond)
         except HGXUnsupported:

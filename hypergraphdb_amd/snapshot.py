@@ -261,6 +261,15 @@ class HyperGraphSnapshot:
         check(lib().hgx_graph_degree(self.handle, ptr(a), len(a), ptr(out)))
         return out
 
+    def type_links(self, types) -> np.ndarray:
+        """The number of LINK atoms of each type key (hgx_graph_type_links, include/hgx_scan.h): the size of
+        the type's segment of the device type index, built on first use -- what a ConditionToQuery.getMetaData
+        reports as sizeExpected for a scanned clause.  0 for an absent key."""
+        t = np.ascontiguousarray(np.atleast_1d(types), np.int32)
+        out = np.zeros(len(t), np.int64)
+        check(lib().hgx_graph_type_links(self.handle, ptr(t), len(t), ptr(out)))
+        return out
+
     def context(self):
         """An execution context of this snapshot (hgx_graph_context): shares the device arrays, has its
         own stream, lock and scratch, so traversals on it run next to the ones on this snapshot (e.g.

@@ -19,7 +19,7 @@ cd "$W"
 # A/B builds read the engine's A/B knobs from the environment (hgx::ab_env, -DHGX_AB_KNOBS); the product
 # library does not
 PIDS=()
-for f in hgx_graph hgx_bfs hgx_query hgx_seq hgx_part hgx_file hgx_paths hgx_union hgx_hops hgx_not; do
+for f in hgx_graph hgx_bfs hgx_query hgx_seq hgx_part hgx_file hgx_paths hgx_union hgx_hops hgx_not hgx_scan; do
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-result -DHGX_AB_KNOBS \
         -I"$ROOT/include" -c $f.hip -o $f.o &
     PIDS+=($!)
