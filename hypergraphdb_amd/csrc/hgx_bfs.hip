@@ -1923,6 +1923,199 @@ __global__ void __launch_bounds__(256) hgx_nonfull_list(int64_t A, const u64* __
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Neighbour hints (HGX_OPT_NF_HINT).  hint[t] = the co-target u != t of largest
+// (degree, id) over every link of inc(t), -1 where there is none: a property of the snapshot.  In a
+// power-law graph that neighbour is a hub, whose level-d row holds nearly every traversal, so on a
+// direct-pull level vis[t] | lvl[hint[t]] decides most listed atoms without a walk over their CSR.
+// ---------------------------------------------------------------------------------------------
+// The best key (degree << 32 | id) among the targets of link L other than t; 0 = none (a target has degree >= 1).
+__device__ __forceinline__ u64 hint_key_of_link(int32_t L, int32_t t, const int64_t* __restrict__ inc_off,
+                                                const int64_t* __restrict__ tgt_off,
+                                                const int32_t* __restrict__ tgt_idx) {
+    u64 best = 0;
+    const int64_t b = tgt_off[L], e = tgt_off[L + 1];
+    for (int64_t p = b; p < e; ++p) {
+        const int32_t u = tgt_idx[p];
+        if (u == t) continue;
+        const int64_t dg = inc_off[u + 1] - inc_off[u];
+        const u64 key = ((u64)(dg < 0xffffffffll ? dg : 0xffffffffll) << 32) | (u64)(uint32_t)u;
+        best = key > best ? key : best;
+    }
+    return best;
+}
+
+// Light atoms (degree <= kHeavyDegree): eight lanes per atom stride over its entries.  The shuffles read
+// lanes of the caller's own group; the loop around them is group-uniform.
+__global__ void __launch_bounds__(256) hgx_nbr_hint(int64_t A, const int64_t* __restrict__ inc_off,
+                                                    const int32_t* __restrict__ inc_row,
+                                                    const int64_t* __restrict__ tgt_off,
+                                                    const int32_t* __restrict__ tgt_idx, int32_t* __restrict__ hint) {
+    const int sub = threadIdx.x & 7;
+    const int64_t grp = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 3;
+    const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) >> 3;
+    for (int64_t t = grp; t < A; t += ngrp) {
+        const int64_t b = inc_off[t], e = inc_off[t + 1];
+        if (e - b > kHeavyDegree) continue;   // hgx_nbr_hint_heavy
+        u64 best = 0;
+        for (int64_t q = b + sub; q < e; q += 8) {
+            const u64 key = hint_key_of_link(inc_row[q], (int32_t)t, inc_off, tgt_off, tgt_idx);
+            best = key > best ? key : best;
+        }
+        for (int off = 4; off > 0; off >>= 1) {
+            const u64 o = __shfl_xor(best, off);
+            best = o > best ? o : best;
+        }
+        if (sub == 0) hint[t] = best ? (int32_t)(uint32_t)best : -1;
+    }
+}
+
+// Heavy atoms by HeavyChunk: a workgroup per chunk, one 64-bit atomicMax per chunk into the atom's slot
+// of hkey (zeroed by the caller); hgx_nbr_hint_heavy_out writes the slots' hints.
+__global__ void __launch_bounds__(256) hgx_nbr_hint_heavy(const HeavyChunk* __restrict__ chunks, int64_t n_chunks,
+                                                          const int64_t* __restrict__ inc_off,
+                                                          const int32_t* __restrict__ inc_row,
+                                                          const int64_t* __restrict__ tgt_off,
+                                                          const int32_t* __restrict__ tgt_idx, u64* __restrict__ hkey) {
+    __shared__ u64 part[4];
+    for (int64_t ci = blockIdx.x; ci < n_chunks; ci += gridDim.x) {   // block-uniform
+        const HeavyChunk c = chunks[ci];
+        u64 best = 0;
+        for (int64_t q = c.beg + threadIdx.x; q < c.end; q += 256) {
+            const u64 key = hint_key_of_link(inc_row[q], c.atom, inc_off, tgt_off, tgt_idx);
+            best = key > best ? key : best;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const u64 o = __shfl_xor(best, off);
+            best = o > best ? o : best;
+        }
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = best;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int k = 1; k < 4; ++k) best = part[k] > best ? part[k] : best;
+            if (best) atomicMax(hkey + c.slot, best);
+        }
+        __syncthreads();   // part is rewritten by the next chunk
+    }
+}
+
+__global__ void __launch_bounds__(256) hgx_nbr_hint_heavy_out(int64_t n_heavy, const int32_t* __restrict__ heavy_atom,
+                                                              const u64* __restrict__ hkey, int32_t* __restrict__ hint) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n_heavy; i += (int64_t)gridDim.x * blockDim.x)
+        hint[heavy_atom[i]] = hkey[i] ? (int32_t)(uint32_t)hkey[i] : -1;
+}
+
+// The hint step of a direct-pull level (symmetric mode, no link-type condition: only there is a co-target
+// of any incident link certainly a neighbour).  A G-lane group takes kNfHintU listed atoms at a time, all
+// of their loads independent of the CSR: hint[t], the frontier bit of the hint, vis[t] and the hint's
+// frontier row.  An atom with vis[t] | lvl[hint] == FULL is written here, with the meaning of the write
+// block of hgx_nf_pull_e (its new row is FULL & ~vis[t] whatever the walk would have read); every other
+// atom goes to the residual list rlist, which the pull kernels then walk as they walked the whole list.
+// A workgroup owns kNfHintChunk consecutive list positions at a time, collects their residual atoms in LDS
+// and claims its rlist range with one atomic (hgx_nonfull_list has the reason).  cCand takes the decided
+// atoms, and again shifted by 32 bits (the host splits the word: stats.nf_hint_atoms); cVisLight and
+// cNfRows take the rows read for every listed atom.  Every branch around a group_any / group_all is
+// group-uniform.
+constexpr int kNfHintU = 4, kNfHintChunk = 1024;
+template <int W>
+__global__ void __launch_bounds__(256) hgx_nf_hint(const int32_t* __restrict__ list, const u64* __restrict__ n_list,
+                                                   const int32_t* __restrict__ hint,
+                                                   const int64_t* __restrict__ inc_off, const u64* __restrict__ fa,
+                                                   const u64* __restrict__ lvl, u64* __restrict__ vis,
+                                                   u64* __restrict__ ever, u64* __restrict__ full,
+                                                   u64* __restrict__ lvl_next, u64* __restrict__ fa_next,
+                                                   u64* __restrict__ ctr, FullMask fm, uint32_t* __restrict__ cpart,
+                                                   int32_t* __restrict__ rlist, u64* __restrict__ n_rlist) {
+    constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G, NG = 256 / G, U = kNfHintU, CH = kNfHintChunk;
+    static_assert(G >= 4 && CH % (NG * U) == 0, "hint step: whole rounds per chunk");
+    typedef Vec<WPL> V;
+    __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
+    __shared__ unsigned int cdone;
+    __shared__ int32_t sres[CH];               // the chunk's residual atoms
+    __shared__ unsigned int scnt;
+    __shared__ u64 sbase;
+    if (cpart) fuse_zero<W>(cplanes, &cdone);
+    const int sub = threadIdx.x & (G - 1), gi = threadIdx.x / G;
+    const typename V::T FULL = full_part<W>(fm, sub);
+    const int64_t n = (int64_t)*n_list;
+    typename V::T cones = V::zero();
+    u64 n_newdeg = 0;
+    uint32_t n_cand = 0, n_vis = 0, n_rows = 0, n_new = 0, n_full = 0;
+    for (int64_t c0 = (int64_t)blockIdx.x * CH; c0 < n; c0 += (int64_t)gridDim.x * CH) {   // block-uniform
+        if (threadIdx.x == 0) scnt = 0u;
+        __syncthreads();
+        for (int r0 = 0; r0 < CH; r0 += NG * U) {
+            int32_t t[U], h[U];
+            bool ok[U], ev[U], on[U];
+            typename V::T old[U], row[U];
+#pragma unroll
+            for (int j = 0; j < U; ++j) {   // consecutive groups read consecutive list entries
+                const int64_t k = c0 + r0 + j * NG + gi;
+                ok[j] = k < n;
+                t[j] = ok[j] ? list[k] : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                h[j] = ok[j] ? hint[t[j]] : -1;
+                ev[j] = ok[j] && bit(ever, t[j]);
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                on[j] = h[j] >= 0 && bit(fa, h[j]);
+                old[j] = ev[j] ? V::ld(vis + (int64_t)t[j] * W + sub * WPL) : V::zero();
+            }
+#pragma unroll
+            for (int j = 0; j < U; ++j) row[j] = on[j] ? V::ld(lvl + (int64_t)h[j] * W + sub * WPL) : V::zero();
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                if (!ok[j]) continue;   // group-uniform
+                const typename V::T all = old[j] | row[j];
+                const bool cov = on[j] && group_all<G>(V::eq(all, FULL));
+                if (sub == 0) {
+                    n_vis += ev[j];
+                    n_rows += on[j];
+                }
+                if (!cov) {   // group-uniform
+                    if (sub == 0) sres[atomicAdd(&scnt, 1u)] = t[j];   // < CH: one slot per list position
+                    continue;
+                }
+                const typename V::T nw = all & ~old[j];
+                if (group_any<G>(V::nz(nw))) {
+                    const int64_t ta = t[j];
+                    V::st(lvl_next + ta * W + sub * WPL, nw);
+                    V::st(vis + ta * W + sub * WPL, all);
+                    if (sub == 0) {
+                        set_bit(fa_next, ta);
+                        if (!ev[j]) set_bit(ever, ta);
+                        set_bit(full, ta);   // all == FULL
+                        ++n_new;
+                        ++n_full;
+                        n_newdeg += (u64)(inc_off[ta + 1] - inc_off[ta]);
+                    }
+                    if (cpart) fuse_add_cs<W>(cplanes, sub, cones, nw);
+                }
+                if (sub == 0) ++n_cand;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) sbase = scnt ? atomicAdd(n_rlist, (u64)scnt) : 0ull;
+        __syncthreads();
+        for (unsigned int i = threadIdx.x; i < scnt; i += 256) rlist[sbase + i] = sres[i];
+        __syncthreads();   // sres / scnt are rewritten by the next chunk
+    }
+    wave_add_sh(ctr + cCand, (u64)n_cand + ((u64)n_cand << 32));   // both halves < 2^31 (atoms are int32)
+    wave_add_sh(ctr + cNewFull, n_full);
+    wave_add_sh(ctr + cVisLight, n_vis);
+    wave_add_sh(ctr + cNewLight, n_new);
+    wave_add_sh(ctr + cNewAtoms, n_new);
+    wave_add_sh(ctr + cNewDeg, n_newdeg);
+    wave_add_sh(ctr + cNfRows, n_rows);
+    if (cpart) {
+        fuse_flush<W>(cplanes, sub, cones);
+        fuse_store<W>(cplanes, &cdone, cpart);
+    }
+}
+
 // The entries [b, e) of one atom's incidence for a G-lane group: acc |= the frontier rows of the entries'
 // targets, G entries a step, leaving once acc | old covers FULL (early).  Shared by hgx_nf_pull and the hub
 // chunks of hgx_nf_pull_heavy; b, e and every branch around a shuffle are group-uniform.
@@ -4515,8 +4708,14 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
             h_new[cNewAtoms] = p.new_global;
             h_new[cNewDeg] = p.part_push;
         }
+        u64 hinted = 0;   // hgx_nf_hint packs the atoms it decided above cCand's own count
+        if (p.kind == 3) {
+            hinted = h_new[cCand] >> 32;
+            h_new[cCand] &= 0xffffffffull;
+        }
         level_ctr.push_back(std::vector<u64>(h_new, h_new + cNum));
         level_ctr.back()[cDirRows] = (u64)p.kind;   // (host-side) kind of this level
+        level_ctr.back().push_back(hinted);         // [cNum]: listed atoms decided by their hint row
         if (!ex) full_deg_total += (int64_t)(h_new[cNewDeg] - h_new[cNewDegNF]);   // incidence of atoms now full
         if (trace)
             std::fprintf(stderr, "[hgx bfs] level %d kind %d allrows %d active_links %llu new %llu push %llu push_nf %llu "
@@ -4650,7 +4849,28 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                 Events e2 = tm.start(kKindNf, d);
                 HGX_HIP(hipMemsetAsync(fa_next, 0, bm_bytes, s));
                 u64* n_list = ctr + (size_t)(max_levels_cap - 1) * kCtrBlock + 8;   // scratch slot
-                HGX_HIP(hipMemsetAsync(n_list, 0, sizeof(u64), s));
+                u64* n_rlist = n_list + 1;                                          //   (the residual list's)
+                HGX_HIP(hipMemsetAsync(n_list, 0, 2 * sizeof(u64), s));
+                // the hint step: only where a co-target of any incident link is certainly a neighbour
+                const bool hinted = g->nf_hint == 1 && nf_opt != 0 && want_type < 0;
+                if (hinted && !g->nbr_hint) {   // once per snapshot
+                    HGX_HIP(hipMalloc(&g->nbr_hint, sizeof(int32_t) * (size_t)std::max<int64_t>(A, 1)));
+                    hgx_nbr_hint<<<grid_for(A * 8, 256, 8192), 256, 0, s>>>(A, g->inc_off, g->inc_row, g->tgt_off,
+                                                                           g->tgt_idx, g->nbr_hint);
+                    HGX_CHECK_LAUNCH();
+                    if (g->n_chunks > 0) {
+                        const size_t hk_bytes = sizeof(u64) * (size_t)g->n_heavy;
+                        u64* hkey = (u64*)g->alloc(hk_bytes);
+                        HGX_HIP(hipMemsetAsync(hkey, 0, hk_bytes, s));
+                        hgx_nbr_hint_heavy<<<(int)std::min<int64_t>(g->n_chunks, 8192), 256, 0, s>>>(
+                            g->chunks, g->n_chunks, g->inc_off, g->inc_row, g->tgt_off, g->tgt_idx, hkey);
+                        HGX_CHECK_LAUNCH();
+                        hgx_nbr_hint_heavy_out<<<grid_for(g->n_heavy, 256, 1024), 256, 0, s>>>(g->n_heavy, g->heavy_atom,
+                                                                                               hkey, g->nbr_hint);
+                        HGX_CHECK_LAUNCH();
+                        g->release(hkey, hk_bytes);   // stream-ordered reuse
+                    }
+                }
                 if (!g->hasinc) {   // once per snapshot
                     HGX_HIP(hipMalloc(&g->hasinc, sizeof(u64) * (size_t)(ceil_div(A, 64) + 1)));
                     hgx_hasinc<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(A, g->inc_off, (u64*)g->hasinc);
@@ -4669,17 +4889,40 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                 // hubs: hgx_nf_pull_e leaves those not covered by their first kHeavyDegree entries to the
                 // chunk kernel and the hub finalise (whose blocks own the partial rows after the pull's)
                 const bool hubs = stepped && g->n_chunks > 0;
+                // The hint step's blocks own the partial rows after those.  Its grid: the workgroups the device
+                // holds at once (2048 ran a second, partly filled round: + 0.17 ms on config 2's level 2;
+                // HGX_NF_HINT_GRID: A/B builds), 256 at least -- a block then stores at most ceil(A / (256 *
+                // chunk)) * chunk rows, below 2^kFusePlanes for any int32 atom count, so the level is fused with
+                // the hint exactly when it is without.
+                static const int hint_resident = [&] {
+                    int per_cu = 0, cus = 0;
+                    HGX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hgx_nf_hint<W>, 256, 0));
+                    HGX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
+                    return std::min(std::max(per_cu * cus, 256), 4096);
+                }();
+                const int hint_grid = hinted ? std::max(ab_int("HGX_NF_HINT_GRID", hint_resident), 256) : 0;
                 if (fuse_ok && fuse_rows_ok(A, nf_grid, 256 / G) &&
-                    (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / G))) {
-                    lv_cblk = nf_grid + (hubs ? hub_grid : 0);
+                    (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / G)) &&
+                    (!hinted || fuse_rows_ok(A, hint_grid, kNfHintChunk))) {
+                    lv_cblk = nf_grid + (hubs ? hub_grid : 0) + hint_grid;
                     lv_cpart = (uint32_t*)g->alloc(cpart_size(lv_cblk));
+                }
+                const int32_t* nf_list = clist;
+                const u64* nf_n = n_list;
+                if (hinted) {   // the atoms their hint row covers are written here, the rest listed again
+                    hgx_nf_hint<W><<<hint_grid, 256, 0, s>>>(
+                        clist, n_list, g->nbr_hint, g->inc_off, fa, lvl, vis, ever, full, lvl_next, fa_next, c, fm,
+                        lv_cpart ? lv_cpart + (size_t)(lv_cblk - hint_grid) * W * 64 : nullptr, flist, n_rlist);
+                    HGX_CHECK_LAUNCH();
+                    nf_list = flist;
+                    nf_n = n_rlist;
                 }
                 u64* resid = nullptr;
                 if (hubs) {
                     resid = (u64*)g->alloc(bm_bytes);
                     HGX_HIP(hipMemsetAsync(resid, 0, bm_bytes, s));
                 }
-#define HGX_NF_ARGS clist, n_list, g->inc_off, g->inc_row, g->inc_type, want_type, g->tgt_off, g->tgt_idx, fa, lvl, vis, \
+#define HGX_NF_ARGS nf_list, nf_n, g->inc_off, g->inc_row, g->inc_type, want_type, g->tgt_off, g->tgt_idx, fa, lvl, vis, \
                     ever, full, lvl_next, fa_next, c, fm, lflags, lv_cpart
                 // (a test per entry with 8 atoms in flight spills: 4 entry slots there)
                 if (nf_e == 1) hgx_nf_pull_e<W, 1, 4><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
@@ -5439,6 +5682,13 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
                 b_pull = A / 8.0 + 24.0 * c[cCand] + 4.0 * A / 64.0 + (8.0 + (typed ? 4.0 : 0.0) + 16.0) * c[cIncLight] +
                          4.0 * c[cActivePins] + A / 8.0 + rowb * c[cNfRows] + rowb * c[cVisLight] +
                          2.0 * rowb * c[cNewLight] + 3.0 * A / 8.0;
+                // the hint step (cNfRows / cVisLight / cNewLight above hold its hint, vis and written rows): the
+                // hint entry of every listed atom, the residual list written and read
+                const double hinted = c.size() > (size_t)cNum ? (double)c[cNum] : 0.0;
+                if (hinted > 0) {
+                    b_pull += 4.0 * c[cCand] + 8.0 * ((double)c[cCand] - hinted);
+                    r->stats.nf_hint_atoms += (int64_t)c[cNum];
+                }
             } else if (fc_level) {   // frontier-code pull: no gather, no lf
                 b_gather = 0.0;
                 // codes: frontier bitmap (twice) + prefixes + the frontier atoms' rows + their codes;

@@ -456,6 +456,8 @@ int hgx_graph_update(hgx_graph* g, int64_t num_atoms, int64_t n_add, const int32
     g->zacc = nullptr;
     if (g->hasinc) (void)hipFree(g->hasinc);
     g->hasinc = nullptr;
+    if (g->nbr_hint) (void)hipFree(g->nbr_hint);
+    g->nbr_hint = nullptr;
     if (g->inc_yf) (void)hipFree(g->inc_yf);
     g->inc_yf = nullptr;
     free_yield_lists(g);

@@ -292,6 +292,7 @@ struct hgx_graph {
     int64_t sp_budget_bytes = (int64_t)48 << 30;    // HGX_OPT_SP_BUDGET (hgx_paths.h): shortest-path working arrays
     int32_t count_fused = 1;                        // HGX_OPT_COUNT_FUSED: dense-level kernels count the rows they store
     int32_t nf_pull = 1;                            // HGX_OPT_NF_PULL: 0 = late levels only, 8-entry step; 1 = the rule; 2 = every eligible level
+    int32_t nf_hint = 1;                            // HGX_OPT_NF_HINT: direct-pull levels try the listed atoms' hint rows first
     unsigned long long* co_vis = nullptr;           // multi-workgroup stage: per-seed visited bitmaps (zero between calls)
     unsigned long long* sc_tab = nullptr;           // order-exact grid stage: level hash, word / key counts (empty between calls)
     int64_t co_vis_seeds = 0, co_pcap = 0;          //   seeds they hold; pair-list capacity (grown on demand)
@@ -315,6 +316,8 @@ struct hgx_graph {
     unsigned long long ctr_seq = 0;          // sequence numbers of those writes
     hipEvent_t pend_ev[2] = {nullptr, nullptr};   // the batched BFS's two in-flight level events
     uint64_t* hasinc = nullptr;          // [A/64 + 1] bit set <=> inc(atom) non-empty (non-full pull levels)
+    int32_t* nbr_hint = nullptr;         // [A] the co-target of largest (degree, id) over the atom's links, -1 = none
+                                         //   (HGX_OPT_NF_HINT: direct-pull levels, made on first use)
     uint8_t* inc_yf = nullptr;           // [I] ordered-mode yield flags per incidence (frontier push), made on first use
     hgx::HeavyChunk* pchunks = nullptr;  // frontier push: kPushChunk-entry chunks of atoms with deg > kPushLight
     int64_t n_pchunks = -1;              // -1 = not built yet

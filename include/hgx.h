@@ -100,7 +100,7 @@ typedef struct hgx_and_query {
 #define HGX_K_PULL_HEAVY    2   /* hgx_atom_pull_heavy      */
 #define HGX_K_HUB_FINALIZE  3   /* hgx_hub_finalize         */
 #define HGX_K_FRONTIER_PUSH 4   /* sparse levels: hgx_frontier_list, hgx_opush[_heavy], hgx_push_finalize_list */
-#define HGX_K_NF_PULL       5   /* late dense levels: hgx_nonfull_list, hgx_nf_pull                        */
+#define HGX_K_NF_PULL       5   /* direct-pull dense levels: hgx_nonfull_list, hgx_nf_hint, hgx_nf_pull     */
 #define HGX_K_FC_PULL       6   /* dense levels over a small frontier: hgx_fc_slots, hgx_fc_codes, hgx_fc_pull */
 #define HGX_K_FC_HEAVY      7   /*   and their hub chunks: hgx_fc_pull_heavy, then hgx_hub_finalize          */
 #define HGX_K_COUNT         8
@@ -158,6 +158,9 @@ typedef struct hgx_bfs_stats {
      * has to count with a pass over the level's rows: not counted by the kernels that wrote them
      * (HGX_OPT_COUNT_FUSED, the frontier-push finalise) and not a whole-graph batch's seed level */
     int64_t count_pass_levels;
+    /* listed atoms of the direct-pull levels (summed over levels and batches) whose row was decided by their
+     * hint neighbour's frontier row, without a walk over their incidence (HGX_OPT_NF_HINT) */
+    int64_t nf_hint_atoms;
 } hgx_bfs_stats;
 
 const char *hgx_version(void);
@@ -555,6 +558,13 @@ int  hgx_shard_graph_create(const hgx_shard *s, int32_t device, hgx_graph **out)
  * a few links, the cover test after every entry; 2 = every eligible dense level (tests, A/B).  The results
  * are the same for every value. */
 #define HGX_OPT_NF_PULL      24
+/* HGX_OPT_NF_HINT (default 1): a direct-pull level of the symmetric generator without a link-type condition
+ * first tries, for every listed atom, the frontier row of one neighbour chosen per snapshot -- the co-target
+ * of largest (degree, id) over the atom's links (hgx_nf_hint; the table is built on first use and dropped by
+ * hgx_graph_update).  Atoms that row covers are written at once; only the rest walk their incidence.
+ * 0 = every listed atom walks its incidence.  The results are the same for both values;
+ * hgx_bfs_stats.nf_hint_atoms counts the atoms the hint decided. */
+#define HGX_OPT_NF_HINT      25
 /* Coalescing statistics of a graph since its creation: device batches run by the packed pattern path
  * and caller batches they served (caller / device = the mean coalescing factor). */
 int  hgx_query_coalesce_stats(hgx_graph *g, int64_t *device_batches, int64_t *caller_batches);

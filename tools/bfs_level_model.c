@@ -3,7 +3,9 @@
  * the cover test acc | vis == FULL.  Per level it prints the frontier, the active links and frontier pins
  * (what the link gather reads), and per exit step E = 1/2/4/8/16 the lf rows a pull of gather + pull
  * reads, the frontier rows a direct pull reads (own row included; entries) and the links whose lf row
- * any pull reads -- light atoms and hubs apart.
+ * any pull reads -- light atoms and hubs apart.  Item 13's hint columns follow: how concentrated the
+ * neighbour hints are, and per level the listed atoms that vis | lvl[hint] covers (with one hint, with a
+ * second), and the entry walk left to the atoms they do not cover, per exit step.
  *   gcc -O3 -fopenmp -o bfs_level_model tools/bfs_level_model.c hypergraphdb_amd/csrc/hgx_gen.c -lm
  *   ./bfs_level_model [scale=0.01] [sources=1024] [depth=4] [nodes=10e6*scale] [links=40e6*scale]   */
 #include <stdint.h>
@@ -19,6 +21,11 @@ int hgx_gen_sources(int64_t n, int64_t P, const int32_t *tgt_idx, int64_t k, uin
 enum { NE = 5, HEAVY = 512 };
 static const int ES[NE] = {1, 2, 4, 8, 16};
 typedef uint64_t u64;
+
+static int cmp_desc(const void *a, const void *b) {
+    const int64_t x = *(const int64_t *)a, y = *(const int64_t *)b;
+    return x < y ? 1 : x > y ? -1 : 0;
+}
 
 int main(int argc, char **argv) {
     const double scale = argc > 1 ? atof(argv[1]) : 0.01;
@@ -49,6 +56,42 @@ int main(int argc, char **argv) {
             io[0] = 0;
         }
     }
+    /* neighbour hints (item 13): per atom the co-targets u != t of largest and second largest (degree, id)
+     * over every link of inc(t), -1 = none -- a property of the snapshot */
+    int32_t *hint1 = malloc(sizeof(int32_t) * N), *hint2 = malloc(sizeof(int32_t) * N);
+    int64_t n_inc = 0;
+#pragma omp parallel for schedule(dynamic, 256) reduction(+ : n_inc)
+    for (int64_t t = 0; t < N; ++t) {
+        u64 k1 = 0, k2 = 0;
+        for (int64_t i = io[t]; i < io[t + 1]; ++i)
+            for (int64_t p = off[inc[i]]; p < off[inc[i] + 1]; ++p) {
+                const int32_t u = tg[p];
+                if (u == t) continue;
+                const u64 key = ((u64)(io[u + 1] - io[u]) << 32) | (uint32_t)u;
+                if (key > k1) { k2 = k1; k1 = key; }
+                else if (key > k2 && key != k1) k2 = key;
+            }
+        hint1[t] = k1 ? (int32_t)(uint32_t)k1 : -1;
+        hint2[t] = k2 ? (int32_t)(uint32_t)k2 : -1;
+        n_inc += io[t + 1] > io[t];
+    }
+    {   /* how concentrated the hints are: distinct hint atoms, and the share served by the top ones */
+        int64_t *use = calloc(N, sizeof(int64_t)), distinct = 0, top = 0;
+        for (int64_t t = 0; t < N; ++t) if (hint1[t] >= 0) ++use[hint1[t]];
+        qsort(use, N, sizeof(int64_t), cmp_desc);
+        while (distinct < N && use[distinct]) ++distinct;
+        printf("hints: %lld atoms with incidence, %lld distinct hint atoms; served by the top", (long long)n_inc, (long long)distinct);
+        const int64_t marks[3] = {64, 1024, 32768};
+        for (int64_t r = 0, m = 0; r < distinct && m < 3; ++r) {
+            top += use[r];
+            if (r + 1 == marks[m] || r + 1 == distinct) {
+                printf(" %lld: %.1f%%", (long long)(r + 1), 100.0 * top / (n_inc ? n_inc : 1));
+                ++m;
+            }
+        }
+        printf("\n");
+        free(use);
+    }
     u64 FULL[16] = {0};
     for (int s = 0; s < S; ++s) FULL[s >> 6] |= 1ull << (s & 63);
     u64 *vis = calloc((size_t)N * W, 8), *lvl = calloc((size_t)N * W, 8), *nxt = calloc((size_t)N * W, 8);
@@ -62,6 +105,8 @@ int main(int argc, char **argv) {
     for (int d = 0; d < depth; ++d) {
         int64_t nf = 0, alinks = 0, fpins = 0, nnew = 0, cand[2] = {0, 0}, k1[2] = {0, 0}, cover[2] = {0, 0};
         int64_t lf[2][NE] = {{0}}, rows[2][NE] = {{0}}, ent[2][NE] = {{0}};
+        /* hints: listed atoms covered by vis | lvl[hint1], by that | lvl[hint2]; the walk left to the rest */
+        int64_t hcov1[2] = {0, 0}, hcov2[2] = {0, 0}, r1ent[NE] = {0}, r1rows[NE] = {0}, r2ent[NE] = {0}, r2rows[NE] = {0};
         for (int64_t v = 0; v < N; ++v) nf += F[v];
 #pragma omp parallel for reduction(+ : alinks, fpins) schedule(static, 4096)
         for (int64_t L = 0; L < M; ++L) {
@@ -72,7 +117,7 @@ int main(int argc, char **argv) {
         }
         memset(used, 0, (size_t)M * NE);
         memset(nxt, 0, (size_t)N * W * 8);
-#pragma omp parallel for schedule(dynamic, 256) reduction(+ : nnew, cand[:2], k1[:2], cover[:2], lf[:2][:NE], rows[:2][:NE], ent[:2][:NE])
+#pragma omp parallel for schedule(dynamic, 256) reduction(+ : nnew, cand[:2], k1[:2], cover[:2], lf[:2][:NE], rows[:2][:NE], ent[:2][:NE], hcov1[:2], hcov2[:2], r1ent[:NE], r1rows[:NE], r2ent[:NE], r2rows[:NE])
         for (int64_t t = 0; t < N; ++t) {
             const int64_t b = io[t], e = io[t + 1], deg = e - b;
             u64 *vt = vis + (size_t)t * W, acc[16] = {0};
@@ -93,6 +138,23 @@ int main(int argc, char **argv) {
             }
             ++cand[h];
             cover[h] += covered;
+            int c1 = 0, c2 = 0;
+            {
+                const int32_t h1 = hint1[t], h2 = hint2[t];
+                u64 a[16];
+                for (int w = 0; w < W; ++w) a[w] = vt[w];
+                if (h1 >= 0 && F[h1]) {
+                    c1 = 1;
+                    for (int w = 0; w < W; ++w) { a[w] |= lvl[(size_t)h1 * W + w]; c1 &= a[w] == FULL[w]; }
+                }
+                c2 = c1;
+                if (!c1 && h2 >= 0 && F[h2]) {
+                    c2 = 1;
+                    for (int w = 0; w < W; ++w) { a[w] |= lvl[(size_t)h2 * W + w]; c2 &= a[w] == FULL[w]; }
+                }
+                hcov1[h] += c1;
+                hcov2[h] += c2;
+            }
             k1[h] += kc;
             for (int64_t i = 0; i < deg && i < (kc + 15) / 16 * 16; ++i) {
                 const int32_t L = inc[b + i];
@@ -103,6 +165,8 @@ int main(int argc, char **argv) {
                     if (i >= stop) continue;
                     ++ent[h][k];
                     rows[h][k] += c;
+                    if (!c1) { ++r1ent[k]; r1rows[k] += c; }
+                    if (!c2) { ++r2ent[k]; r2rows[k] += c; }
                     if (c) { ++lf[h][k]; used[(size_t)L * NE + k] = 1; }
                 }
             }
@@ -123,6 +187,11 @@ int main(int argc, char **argv) {
                 printf("    E=%-2d entries %lld  lf rows %lld  direct rows %lld\n", ES[k], (long long)ent[h][k],
                        (long long)lf[h][k], (long long)rows[h][k]);
         }
+        printf("  hints: covered by vis | lvl[hint] light %lld hubs %lld; with a second hint light %lld hubs %lld\n",
+               (long long)hcov1[0], (long long)hcov1[1], (long long)hcov2[0], (long long)hcov2[1]);
+        for (int k = 0; k < NE; ++k)
+            printf("    E=%-2d walk left after one hint: entries %lld direct rows %lld; after two: entries %lld direct rows %lld\n",
+                   ES[k], (long long)r1ent[k], (long long)r1rows[k], (long long)r2ent[k], (long long)r2rows[k]);
         for (int k = 0; k < NE; ++k) {
             int64_t u = 0;
             for (int64_t L = 0; L < M; ++L) u += used[(size_t)L * NE + k];

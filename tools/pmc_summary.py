@@ -38,6 +38,9 @@ from collections import defaultdict
 KIND = {"hgx_link_gather2": "hgx_link_gather", "hgx_atom_pull2": "hgx_atom_pull", "hgx_nf_pull_e": "hgx_nf_pull"}
 
 
+PART_OF = {"hgx_nf_hint": "hgx_nf_pull"}   # the hint step of a direct-pull level
+
+
 def short(name):
     m = re.search(r"\b(hgx_[A-Za-z0-9_]+|k_[A-Za-z0-9_]+)\b", name)
     if m:
@@ -173,6 +176,15 @@ def main():
         js["kernels"][k] = {"launches": len(t), "avg_ms": avg, "fetch_bytes_per_launch": fb,
                             "write_bytes_per_launch": wb, "hbm_bytes_per_launch": hbm,
                             "hbm_GBps": (hbm / (avg / 1e3) / 1e9) if hbm else None}
+    # a kernel that runs once per launch of an engine kind, in front of the kind's own kernel: the kind's
+    # per-launch figures are the two summed (the kernel keeps its own entry)
+    for k, kind in PART_OF.items():
+        a, b = js["kernels"].get(k), js["kernels"].get(kind)
+        if a and b and a["launches"] == b["launches"] and a["hbm_bytes_per_launch"] and b["hbm_bytes_per_launch"]:
+            for key in ("avg_ms", "fetch_bytes_per_launch", "write_bytes_per_launch", "hbm_bytes_per_launch"):
+                b[key] = (b[key] or 0) + (a[key] or 0)
+            b["hbm_GBps"] = b["hbm_bytes_per_launch"] / (b["avg_ms"] / 1e3) / 1e9
+            b["includes"] = k
     with open(os.path.join(prof, f"pmc_{workload}.json"), "w") as f:
         json.dump(js, f, indent=1)
     with open(os.path.join(prof, f"{tag}_summary.md"), "w") as f:
