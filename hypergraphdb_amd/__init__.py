@@ -7,7 +7,9 @@ This package is the host-side mirror of the reference interfaces on that path:
   query                         hg.and/or/type/incident/orderedLink, GpuAndToQuery, GpuOrToQuery, pattern_batch,
                                 pattern_batch_dnf (include/hgx_dnf.h); hg.not_ on its clauses (include/hgx_not.h);
                                 opt-in type-index scans of clauses without an anchor: pattern_batch_dnf(...,
-                                type_scan=True), GpuScanToQuery (include/hgx_scan.h)
+                                type_scan=True), GpuScanToQuery (include/hgx_scan.h); hg.apply(hg.targetAt) and
+                                the And of such projections on the device: pattern_batch_join, join_parts,
+                                GpuMapToQuery (include/hgx_join.h)
   classics                      GraphClassics.dijkstra / shortest_paths (include/hgx_paths.h);
                                 hop_paths -> HopPaths, BfsResult.paths / depths / predecessors: unit-weight
                                 shortest paths read out of a batched BFS (include/hgx_hops.h)
@@ -17,9 +19,10 @@ from .algorithms import (AtomTypeCondition, BfsResult, DefaultALGenerator, HGBre
                          HopPaths, SequenceResult, bfs_sequence,
                          HGException, bfs_batch)
 from .classics import GraphClassics, LinkWeights, ShortestPathsResult, hop_paths, shortest_paths  # noqa: F401
-from .query import (And, ArityCondition, GpuAndToQuery, GpuOrToQuery, GpuScanToQuery, HGQueryConfiguration, LinkCondition,  # noqa: F401
-                    Not, Or, PositionedIncidentCondition, TypePlusCondition, find_all, hg, pattern_batch,
-                    pattern_batch_dnf, to_dnf)
+from .query import (And, ArityCondition, GpuAndToQuery, GpuMapToQuery, GpuOrToQuery, GpuScanToQuery,  # noqa: F401
+                    HGQueryConfiguration, LinkCondition, MapCondition, Not, Or, PositionedIncidentCondition, TargetAt,
+                    TypePlusCondition, find_all, hg, join_parts, pattern_batch, pattern_batch_dnf, pattern_batch_join,
+                    to_dnf)
 from .snapshot import HyperGraphSnapshot, export_store, rank_handles, read_snapshot, write_snapshot  # noqa: F401
 
 __version__ = "0.1.0"

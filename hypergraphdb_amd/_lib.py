@@ -94,6 +94,11 @@ EXPORTED_NOT = ("hgx_pattern_batch_dnf_not", "hgx_query_result_not_stats")
 # Every symbol include/hgx_scan.h declares (checked by tests/test_scan_ref.py without a GPU).
 EXPORTED_SCAN = ("hgx_pattern_batch_dnf_scan", "hgx_query_result_scan_stats", "hgx_graph_type_links")
 
+# Every symbol include/hgx_join.h declares (checked by tests/test_join_ref.py without a GPU).
+EXPORTED_JOIN = ("hgx_pattern_batch_join", "hgx_query_result_join_stats")
+HGX_JOIN_SELF = -1
+HGX_JOIN_TYPE_SCAN = 1
+
 # Every symbol include/hgx_hops.h declares (checked by tests/test_hop_ref.py without a GPU).
 EXPORTED_HOPS = (
     "hgx_bfs_result_paths", "hgx_hop_paths_info", "hgx_hop_paths_offsets", "hgx_hop_paths_read", "hgx_hop_paths_stats",
@@ -279,6 +284,11 @@ def lib():
         "hgx_query_result_scan_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
                                          C.POINTER(C.c_double)], C.c_int),
         "hgx_graph_type_links": ([vp, vp, i64, vp], C.c_int),
+        # include/hgx_join.h
+        "hgx_pattern_batch_join": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                    i32, C.POINTER(vp)], C.c_int),
+        "hgx_query_result_join_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
         # include/hgx_hops.h
         "hgx_bfs_result_paths": ([vp, vp, vp, i32, C.POINTER(vp)], C.c_int),
         "hgx_hop_paths_info": ([vp, C.POINTER(i32), C.POINTER(i64)], C.c_int),

@@ -27,6 +27,7 @@
 
 #include "../../include/hgx_dnf.h"
 #include "../../include/hgx_hops.h"
+#include "../../include/hgx_join.h"
 #include "../../include/hgx_not.h"
 #include "../../include/hgx_paths.h"
 #include "../../include/hgx_scan.h"
@@ -478,6 +479,48 @@ struct UnionArgs {
 size_t union_temp_bytes(int64_t cap, hipStream_t s);
 // Enqueues the union on s: no synchronisation, nothing read back by the host.
 void union_launch(const UnionArgs& a, hipStream_t s);
+
+// The join stage of a join batch (hgx_pattern_batch_join, include/hgx_join.h; hgx_join.hip)
+// behind the union, which then leaves its offsets and ids in device memory: the "queries" of the union are the
+// parts of the join queries.  Everything but the out_* pointers (the mapped result area) is device memory; ctr
+// is zeroed by the launcher.  keep / pre / tmp may be the union's (it is done with them).
+struct JoinArgs {
+    int32_t n_queries, n_parts;
+    const int64_t* part_off;     // [n_queries + 1] parts of each join query
+    const int32_t* part_pos;     // [n_parts] target position of each part, HGX_JOIN_SELF = the link atom
+    const int64_t* uoff;         // [n_parts + 1] the union's result offsets (one result per part)
+    const int32_t* uids;         // [cap] the union's result ids (link atoms)
+    int64_t cap;                 // workspace capacity in hits (the grids, the sort and the scan are sized from it)
+    const int64_t* stat;         // [8] statistics of the clause stage: [2] overflow
+    int64_t M;                   // the snapshot's link rows
+    const int32_t* link_atom;
+    const int64_t* tgt_off;
+    const int32_t* tgt_idx;
+    u64* key;                    // [cap] (part << 32) | value; past the hits a pad key that sorts last
+    u64* key_sorted;             // [cap]
+    int32_t sort_bits;           // the sort covers the low 32 + bits(n_parts) bits
+    void* sort_tmp;              // radix sort temporary storage (join_temp_bytes)
+    size_t sort_tmp_bytes;
+    uint8_t* keep;               // [cap + 1] keep flags of the sorted keys
+    int64_t* pre;                // [cap + 1] their exclusive prefix sum
+    void* tmp;                   // scan temporary storage (union_temp_bytes)
+    size_t tmp_bytes;
+    unsigned long long* ctr;     // [8] hits projected, distinct values, -, key probes, keep probes, targets read
+    unsigned long long* out_ctr; // [8] mapped: ctr, [2] = ids kept
+    int64_t* out_off;            // [n_queries + 1] mapped: result offsets
+    int32_t* out_ids;            // [cap] mapped: result ids (atoms)
+};
+// Bits of the part field of a key: enough for the pad key's part, n_parts.
+inline int32_t join_part_bits(int64_t n_parts) {
+    int32_t b = 1;
+    while (b < 31 && ((int64_t)1 << b) <= n_parts) ++b;
+    return b;
+}
+size_t join_temp_bytes(int64_t cap, int32_t sort_bits, hipStream_t s);
+// Enqueues the join on s: no synchronisation, nothing read back by the host.
+void join_launch(const JoinArgs& a, hipStream_t s);
+// The host checks of the join arrays (hgx_join.hip): HGX_E_INVALID naming the join query and the part.
+void join_validate(int32_t n_queries, const int64_t* part_off, const int32_t* part_pos, int32_t flags);
 
 // The negation program of a DNF batch (hgx_pattern_batch_dnf_not, include/hgx_not.h) as the caller handed
 // it over; not_validate fills the totals.

@@ -1075,6 +1075,10 @@ struct hgx_query_result {
     // hgx_pattern_batch_dnf_scan: scanned clauses, index rows they covered / kept, device ms and algorithmic bytes
     int64_t clauses_scanned = 0, rows_scanned = 0, rows_kept = 0;
     double ms_scan = 0, bytes_scan = 0;
+    // hgx_pattern_batch_join: parts, hits projected, distinct values of the parts, ids kept, device ms and
+    // algorithmic bytes of the join stage
+    int64_t join_parts = 0, hits_projected = 0, values_distinct = 0, join_kept = 0;
+    double ms_join = 0, bytes_join = 0;
 };
 
 // A packed batch resident in device memory (hgx_query_set_create), in the staging layout of the
@@ -1137,6 +1141,14 @@ struct ScanPlan {
     int32_t clauses = 0;                  // every scanned clause
     bool anchored = false;                // the batch has an anchored clause
     bool anchored_negs = false;           //   ... one with a negation (the filter stage runs)
+};
+
+// The join stage's part of one batch (hgx_pattern_batch_join): the Or queries of the DNF batch are the parts of
+// n_queries join queries (validated by join_validate).
+struct JoinPlan {
+    int32_t n_queries = 0;
+    const int64_t* part_off = nullptr;   // [n_queries + 1]
+    const int32_t* part_pos = nullptr;   // [part_off[n_queries]]
 };
 
 template <class Get>
@@ -1413,6 +1425,10 @@ struct Front {
     const ScanDesc* scan_desc = nullptr;   //   device copies
     const int64_t* scan_chunk_beg = nullptr;
     const int64_t* scan_clause_chunk = nullptr;
+    // ... with a join stage behind the union (hgx_pattern_batch_join): n_or counts the parts
+    const JoinPlan* join = nullptr;
+    const int64_t* join_part_off = nullptr;   //   device copies
+    const int32_t* join_part_pos = nullptr;
 };
 
 // Buffers taken from the graph pool for one call, released on every exit path.
@@ -1435,6 +1451,7 @@ struct Events {
     hipEvent_t u = nullptr;   // start of the union stage (DNF batches only: taken on first use)
     hipEvent_t nt = nullptr;  // start of the negation filter (DNF batches with negations only)
     hipEvent_t sn = nullptr;  // start of the scan stage (DNF batches with scanned clauses only)
+    hipEvent_t jn = nullptr;  // start of the join stage (join batches only)
     bool on = false;
     void init(hgx_graph* gg) {
         g = gg;
@@ -1465,12 +1482,14 @@ struct Events {
     void rec_union(hipStream_t s) { rec_extra(u, s); }
     void rec_not(hipStream_t s) { rec_extra(nt, s); }
     void rec_scan(hipStream_t s) { rec_extra(sn, s); }
+    void rec_join(hipStream_t s) { rec_extra(jn, s); }
     ~Events() {
         for (int i = 0; i < 4; ++i)
             if (e[i]) g->ev_pool.push_back(e[i]);
         if (u) g->ev_pool.push_back(u);
         if (nt) g->ev_pool.push_back(nt);
         if (sn) g->ev_pool.push_back(sn);
+        if (jn) g->ev_pool.push_back(jn);
     }
 };
 
@@ -1508,6 +1527,9 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     const ScanPlan* sp = f.scan && f.scan->n_chunks > 0 ? f.scan : nullptr;
     const size_t o_sd = sp ? u.take(bytes_of(sp->desc)) : 0, o_sb = sp ? u.take(bytes_of(sp->chunk_beg)) : 0,
                  o_sc = sp ? u.take(bytes_of(sp->clause_chunk)) : 0;
+    const JoinPlan* jp = f.join;
+    const size_t o_jo = jp ? u.take(sizeof(int64_t) * ((size_t)jp->n_queries + 1)) : 0,
+                 o_jp = jp ? u.take(sizeof(int32_t) * (size_t)f.n_or) : 0;
     char* h = (char*)g->pinned_buf(u.off);
     auto put = [&](size_t o, const auto& v) {
         if (!v.empty()) std::memcpy(h + o, v.data(), sizeof(v[0]) * v.size());
@@ -1525,6 +1547,10 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
         put(o_sc, sp->clause_chunk);
     }
     if (f.n_or >= 0) std::memcpy(h + o_cl, f.clause_off_h, sizeof(int64_t) * ((size_t)f.n_or + 1));
+    if (jp) {
+        std::memcpy(h + o_jo, jp->part_off, sizeof(int64_t) * ((size_t)jp->n_queries + 1));
+        if (f.n_or > 0) std::memcpy(h + o_jp, jp->part_pos, sizeof(int32_t) * (size_t)f.n_or);
+    }
     if (np) {
         const int64_t zero = 0;   // (a program without terms has no lit_off)
         std::memcpy(h + o_ng, np->neg_off, sizeof(int64_t) * ((size_t)n + 1));
@@ -1557,6 +1583,10 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
         f.scan_desc = (const ScanDesc*)(d + o_sd);
         f.scan_chunk_beg = (const int64_t*)(d + o_sb);
         f.scan_clause_chunk = (const int64_t*)(d + o_sc);
+    }
+    if (jp) {
+        f.join_part_off = (const int64_t*)(d + o_jo);
+        f.join_part_pos = (const int32_t*)(d + o_jp);
     }
     f.cond_bytes = 20.0 * nb.anchors.size() + 4.0 * nb.types.size() + 4.0 * nb.pos.size() +
                    4.0 * nb.pattern.size() + (double)sizeof(QDesc) * n;
@@ -1692,9 +1722,12 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         const bool neg = dnf && f.neg.neg_off && (!f.scan || f.scan->anchored_negs);
         // ... with scanned clauses: the scan's eight counters after the filter's
         const bool scan = dnf && f.scan && f.scan->n_chunks > 0;
-        const size_t m_stat = 0, m_ctr = 64, m_nctr = 160, m_sctr = 224,
-                     m_qoff = dnf ? (f.scan ? 288 : neg ? 224 : 160) : 128;
-        const size_t m_ids = m_qoff + ((8 * (size_t)(nq + 1) + 15) & ~(size_t)15);
+        // ... with a join stage: its eight counters after the scan's, and the result's queries are the join queries
+        const JoinPlan* jp = dnf ? f.join : nullptr;
+        const int32_t nres = jp ? jp->n_queries : nq;
+        const size_t m_stat = 0, m_ctr = 64, m_nctr = 160, m_sctr = 224, m_jctr = 288,
+                     m_qoff = dnf ? (jp ? 352 : f.scan ? 288 : neg ? 224 : 160) : 128;
+        const size_t m_ids = m_qoff + ((8 * (size_t)(nres + 1) + 15) & ~(size_t)15);
         char* hm = (char*)g->mapped_buf(m_ids + 4 * (size_t)capK);
         void* hmd = nullptr;
         HGX_HIP(hipHostGetDevicePointer(&hmd, hm, 0));
@@ -1784,6 +1817,38 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             un.run_off = sa.run_out;
             un.hits = sa.hits_out;
         }
+        // a join batch: the union leaves the parts' results in device memory and the join stage publishes the
+        // result area (hgx_join.hip); its flags, prefix sums and scan storage are the union's
+        JoinArgs ja{};
+        if (jp) {
+            ja.n_queries = jp->n_queries;
+            ja.n_parts = nq;
+            ja.part_off = f.join_part_off;
+            ja.part_pos = f.join_part_pos;
+            ja.cap = capK;
+            ja.stat = stat_d;
+            ja.M = g->M;
+            ja.link_atom = g->link_atom;
+            ja.tgt_off = g->tgt_off;
+            ja.tgt_idx = g->tgt_idx;
+            ja.key = (u64*)w.take(sizeof(u64) * (size_t)capK);
+            ja.key_sorted = (u64*)w.take(sizeof(u64) * (size_t)capK);
+            ja.sort_bits = 32 + join_part_bits(nq);
+            ja.sort_tmp_bytes = join_temp_bytes(capK, ja.sort_bits, s);
+            ja.sort_tmp = w.take(ja.sort_tmp_bytes);
+            ja.keep = un.keep;
+            ja.pre = un.pre;
+            ja.tmp = un.tmp;
+            ja.tmp_bytes = un.tmp_bytes;
+            ja.ctr = (u64*)w.take(sizeof(u64) * 8);
+            ja.out_ctr = (u64*)(rd + m_jctr);
+            ja.out_off = un.out_off;
+            ja.out_ids = un.out_ids;
+            un.out_off = (int64_t*)w.take(sizeof(int64_t) * ((size_t)nq + 1));
+            un.out_ids = (int32_t*)w.take(sizeof(int32_t) * (size_t)capK);
+            ja.uoff = un.out_off;
+            ja.uids = un.out_ids;
+        }
         const int64_t nbp = std::max<int64_t>(1, ceil_div(capC, kPlaceChunks));
         // derived flat index: no scan launch between the front kernel and the match (its counter shards
         // were zeroed by the front kernel; a re-run after a workspace overflow zeroes them here)
@@ -1852,6 +1917,10 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             ev.rec_union(s);
             union_launch(un, s);
         }
+        if (jp) {
+            ev.rec_join(s);
+            join_launch(ja, s);
+        }
         ev.rec(3, s);
         if (flag) {
             const u64* fl = (const u64*)(hm + m_stat) + 7;
@@ -1880,13 +1949,14 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             g->q_cap_cand = std::max<int64_t>(capK, stat[1] + stat[1] / 4 + 4096);
             continue;
         }
-        const int64_t total = stat[3];
+        const u64* jc = (const u64*)(hm + m_jctr);   // (a join batch: the join stage's counters, [2] its ids kept)
+        const int64_t total = jp ? (int64_t)jc[2] : stat[3];
         r->n_hits = total;
         if (r->ext_off) {   // caller buffers: no result vectors
-            std::memcpy(r->ext_off, qoff_h, sizeof(int64_t) * (nq + 1));
+            std::memcpy(r->ext_off, qoff_h, sizeof(int64_t) * (nres + 1));
             if (total <= r->ext_cap && total > 0) std::memcpy(r->ext_ids, ids_h, sizeof(int32_t) * total);
         } else {
-            std::memcpy(r->offsets.data(), qoff_h, sizeof(int64_t) * (nq + 1));
+            std::memcpy(r->offsets.data(), qoff_h, sizeof(int64_t) * (nres + 1));
             r->ids.assign(ids_h, ids_h + total);
         }
         if (dnf) {
@@ -1896,14 +1966,36 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             // in the placement; the clause and query offset tables once, + the query offsets written
             const u64* uc = ctr_h + qNum;
             r->clause_hits = stat[6];
-            r->kept = total;
-            r->bytes_union = 15.0 * (double)stat[6] + 8.0 * (double)total + 4.0 * ((double)uc[0] + (double)uc[2]) +
+            r->kept = stat[3];
+            r->bytes_union = 15.0 * (double)stat[6] + 8.0 * (double)stat[3] + 4.0 * ((double)uc[0] + (double)uc[2]) +
                              16.0 * (double)uc[1] + 32.0 * (double)uc[3] + 8.0 * ((double)n + 1) +
                              24.0 * ((double)nq + 1);
             if (ev.on) {
                 float c = 0;
-                HGX_HIP(hipEventElapsedTime(&c, ev.u, ev.e[3]));
+                HGX_HIP(hipEventElapsedTime(&c, ev.u, jp ? ev.jn : ev.e[3]));
                 r->ms_union = c;
+            }
+        }
+        if (jp) {
+            // algorithmic bytes of the join stage: per hit its id read and its key written
+            // (12 B), 8 B per probe of the part offsets and 4 B per probe of link_atom (counted together at
+            // 8 B), the row's offset pair and target per target read (20 B); a pad key per unused slot (8 B);
+            // the sort: every slot read and written once per 8-bit pass (16 B); per sorted key the key, its
+            // predecessor and its flag (17 B) and 8 B per probe of the keep; the scan: flag read, prefix
+            // written (9 B per slot); the placement: flag, prefix (9 B) per hit, key read and id written (12 B)
+            // per id kept; the part tables and the query offsets
+            const double H = (double)jc[0], slots = (double)capK, passes = (double)((ja.sort_bits + 7) / 8);
+            r->join_parts = nq;
+            r->hits_projected = (int64_t)jc[0];
+            r->values_distinct = (int64_t)jc[1];
+            r->join_kept = total;
+            r->bytes_join = 12.0 * H + 8.0 * (double)jc[3] + 20.0 * (double)jc[5] + 8.0 * (slots - H) +
+                            16.0 * slots * passes + 17.0 * H + 8.0 * (double)jc[4] + 9.0 * (slots + 1) + 9.0 * H +
+                            12.0 * (double)total + 12.0 * (double)nq + 24.0 * ((double)nres + 1);
+            if (ev.on) {
+                float c = 0;
+                HGX_HIP(hipEventElapsedTime(&c, ev.jn, ev.e[3]));
+                r->ms_join = c;
             }
         }
         int64_t scan_kept = 0;
@@ -2067,13 +2159,14 @@ void plan_scan(hgx_graph* g, int32_t n, const NormBatch& nb, const NotProgram* n
 }
 
 int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t n, NormBatch& nb,
-                  hgx_query_result** out, const NotProgram* neg = nullptr) {
+                  hgx_query_result** out, const NotProgram* neg = nullptr, const JoinPlan* join = nullptr) {
     HGX_API_BEGIN
     const bool prof = trace_env("HGX_QUERY_PROFILE");
     const double t0 = now_ms();
     std::unique_ptr<hgx_query_result> r(new hgx_query_result());
-    r->n = n_or;
-    r->offsets.assign((size_t)n_or + 1, 0);
+    r->n = join ? join->n_queries : n_or;   // (a join batch: the Or queries are the parts of the join queries)
+    r->offsets.assign((size_t)r->n + 1, 0);
+    if (join) r->join_parts = n_or;
     if (n > 0) {
         std::lock_guard<std::mutex> lk(g->mu);
         HGX_HIP(hipSetDevice(g->device));
@@ -2086,6 +2179,7 @@ int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t
         f.n_or = n_or;
         f.clause_off_h = clause_off;
         f.neg_h = neg;   // (validated, with at least one negation; nullptr: a plain DNF batch)
+        f.join = join;
         ScanPlan sp;
         if (!nb.scan.empty()) {   // (hgx_pattern_batch_dnf_scan only; none: exactly hgx_pattern_batch_dnf_not)
             plan_scan(g, n, nb, neg, sp);
@@ -2326,7 +2420,8 @@ void hgx_query_result_free(hgx_query_result* r) { delete r; }
 static int dnf_entry(hgx_graph* g, int32_t n_queries, const int64_t* clause_off, const int64_t* type_off,
                      const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
                      const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
-                     const int32_t* arity, NotProgram* neg, hgx_query_result** out, bool scan = false) {
+                     const int32_t* arity, NotProgram* neg, hgx_query_result** out, bool scan = false,
+                     const JoinPlan* join = nullptr) {
     HGX_API_BEGIN
     if (!g || !out || n_queries < 0 || !clause_off) fail(HGX_E_INVALID, "hgx_pattern_batch_dnf: bad argument");
     *out = nullptr;
@@ -2363,7 +2458,7 @@ static int dnf_entry(hgx_graph* g, int32_t n_queries, const int64_t* clause_off,
                   in.arity = arity[q];
               },
               nb);
-    return run_batch_dnf(g, n_queries, clause_off, n, nb, out, neg);
+    return run_batch_dnf(g, n_queries, clause_off, n, nb, out, neg, join);
     HGX_API_END
 }
 
@@ -2407,6 +2502,61 @@ int hgx_pattern_batch_dnf_scan(hgx_graph* g, int32_t n_queries, const int64_t* c
     p.n_ops = n_ops;
     return dnf_entry(g, n_queries, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat, arity,
                      neg_off ? &p : nullptr, out, true);
+}
+
+// hgx_pattern_batch_join (include/hgx_join.h): the parts are the queries of a DNF batch with a join plan.  An
+// error of the DNF entry names the part as its "query"; the message is put behind the join query and the part.
+int hgx_pattern_batch_join(hgx_graph* g, int32_t n_queries, const int64_t* part_off, const int32_t* part_pos,
+                           const int64_t* clause_off, const int64_t* type_off, const int32_t* types,
+                           const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off, const int32_t* pos,
+                           const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat, const int32_t* arity,
+                           const int64_t* neg_off, const int64_t* term_off, const int64_t* lit_off, const int32_t* lit,
+                           const int32_t* ops, int64_t n_ops, int32_t flags, hgx_query_result** out) {
+    HGX_API_BEGIN
+    if (!g || !out) fail(HGX_E_INVALID, "hgx_pattern_batch_join: bad argument");
+    *out = nullptr;
+    join_validate(n_queries, part_off, part_pos, flags);
+    if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch_join: not available on a partition shard");
+    JoinPlan jp;
+    jp.n_queries = n_queries;
+    jp.part_off = part_off;
+    jp.part_pos = part_pos;
+    NotProgram p;
+    p.neg_off = neg_off;
+    p.term_off = term_off;
+    p.lit_off = lit_off;
+    p.lit = lit;
+    p.ops = ops;
+    p.n_ops = n_ops;
+    const int32_t n_parts = (int32_t)part_off[n_queries];
+    const int rc = dnf_entry(g, n_parts, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat,
+                             arity, neg_off ? &p : nullptr, out, (flags & HGX_JOIN_TYPE_SCAN) != 0, &jp);
+    if (rc != HGX_OK) {
+        std::string msg = hgx_last_error(), at;
+        const size_t k = msg.find("query ");
+        if (k != std::string::npos && k + 6 < msg.size() && msg[k + 6] >= '0' && msg[k + 6] <= '9') {
+            const int64_t s = std::strtoll(msg.c_str() + k + 6, nullptr, 10);
+            if (s >= 0 && s < n_parts) {
+                const int64_t j = std::upper_bound(part_off, part_off + n_queries + 1, s) - part_off - 1;
+                at = "join query " + std::to_string(j) + " part " + std::to_string(s - part_off[j]) + ": ";
+            }
+        }
+        fail(rc, "hgx_pattern_batch_join: " + at + msg);
+    }
+    HGX_API_END
+}
+
+int hgx_query_result_join_stats(const hgx_query_result* r, int64_t* parts, int64_t* hits_projected,
+                                int64_t* values_distinct, int64_t* kept, double* ms_join, double* bytes_join) {
+    HGX_API_BEGIN
+    if (!r) fail(HGX_E_INVALID, "hgx_query_result_join_stats: null result");
+    if (parts) *parts = r->join_parts;
+    if (hits_projected) *hits_projected = r->hits_projected;
+    if (values_distinct) *values_distinct = r->values_distinct;
+    if (kept) *kept = r->join_kept;
+    if (ms_join) *ms_join = r->ms_join;
+    if (bytes_join) *bytes_join = r->bytes_join;
+    HGX_API_END
 }
 
 int hgx_query_result_scan_stats(const hgx_query_result* r, int64_t* clauses_scanned, int64_t* rows_scanned,

@@ -23,6 +23,13 @@ Reference (C = core/src/java/org/hypergraphdb):
     TYPES OF LINK ATOMS ONLY: a scanned clause delivers the LINK atoms of the type that pass its predicates;
     indexByType.find(T) also returns node atoms of type T.  The two agree whenever T has no node instances --
     the caller opts in knowing that, and nothing routes a clause to the scan by default.
+  * hg.apply(hg.targetAt(graph, i), cond): ToQueryMap compiles a MapCondition to a ResultMapQuery over cond's
+    query (C/query/cond2qry/ToQueryMap.java:409-427) whose mapping ends in LinkProjectionMapping.eval =
+    link.getTargetAt(i) (C/query/impl/LinkProjectionMapping.java:33-36); the And of two such conditions is the
+    reference's pattern test (testcore PatternTests.java:20-61).  Here: join_parts + pattern_batch_join, one
+    device call through hgx_pattern_batch_join (include/hgx_join.h) -- the sorted SET of the projected atoms (the
+    reference delivers duplicates in the inner order), a link too short for i contributing nothing (the
+    reference's getTargetAt throws ArrayIndexOutOfBoundsException there).
 """
 from __future__ import annotations
 
@@ -555,8 +562,11 @@ def decode_negations(neg_off, term_off, lit_off, lit, ops):
 
 
 class QueryResult:
-    def __init__(self, offsets, ids, ms=None, union=None, negation=None, scan=None):
+    def __init__(self, offsets, ids, ms=None, union=None, negation=None, scan=None, join=None):
         self.offsets, self.ids, self.ms = offsets, ids, ms
+        # pattern_batch_join: {"parts", "hits_projected", "values_distinct", "kept", "ms_join", "bytes_join"}
+        # (hgx_query_result_join_stats; all zero on a pattern_batch_dnf result)
+        self.join = join
         # pattern_batch_dnf(type_scan=True): {"clauses_scanned", "rows_scanned", "rows_kept", "ms_scan",
         # "bytes_scan"} (hgx_query_result_scan_stats)
         self.scan = scan
@@ -721,10 +731,16 @@ def _read_dnf_result(h, n, scan=False) -> QueryResult:
     cs, rs, rk, ms_s, by_s = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
     rc3 = lib().hgx_query_result_scan_stats(h, C.byref(cs), C.byref(rs), C.byref(rk), C.byref(ms_s),
                                             C.byref(by_s)) if scan else _lib.HGX_OK
+    pa, hp, vd, jk, ms_j, by_j = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    rc4 = lib().hgx_query_result_join_stats(h, C.byref(pa), C.byref(hp), C.byref(vd), C.byref(jk), C.byref(ms_j),
+                                            C.byref(by_j))
     r = _read_result(h, n)   # frees the result
     check(rc)
     check(rc2)
     check(rc3)
+    check(rc4)
+    r.join = {"parts": pa.value, "hits_projected": hp.value, "values_distinct": vd.value, "kept": jk.value,
+              "ms_join": ms_j.value, "bytes_join": by_j.value}
     if scan:
         r.scan = {"clauses_scanned": cs.value, "rows_scanned": rs.value, "rows_kept": rk.value, "ms_scan": ms_s.value,
                   "bytes_scan": by_s.value}
@@ -800,6 +816,121 @@ def split_type_scan(norm, negs):
     return [(dict(norm, types=[t]), negs) for t in norm["types"]]
 
 
+def _lower_dnf_query(q, type_scan, norm, negs):
+    """One query of pattern_batch_dnf -- a condition, or a list of normalised clauses -- appended to ``norm`` /
+    ``negs`` as the clauses the engine takes."""
+    for c in (q if type(q) in (list, tuple) else [normalize_clause(c) for c in to_dnf(q)]):
+        c, ng = c if type(c) is tuple else (c, [])
+        for c1, ng1 in (split_type_scan(c, ng) if type_scan else [(c, ng)]):
+            norm.append(c1)
+            negs.append([] if c1 == "empty" else ng1)   # (an "empty" clause runs as a NOP: nothing to filter)
+
+
+# --- hg.apply(hg.targetAt): projections of pattern hits and their intersection (include/hgx_join.h) --------
+
+JOIN_SELF = _lib.HGX_JOIN_SELF
+
+
+def _same_store(a, b) -> bool:
+    """``a`` and ``b`` are one snapshot or execution contexts of one (they share the host mirror)."""
+    mirror = getattr(a, "tgt_off", None)
+    return a is b or (mirror is not None and mirror is getattr(b, "tgt_off", None))
+
+
+def _check_part(c, whole):
+    if isinstance(c, (MapCondition, BFSCondition)):
+        raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"{type(c).__name__} inside a part of {whole!r}")
+    if isinstance(c, (And, Or)):
+        for x in c:
+            _check_part(x, whole)
+    elif isinstance(c, Not):
+        _check_part(c.negated, whole)
+
+
+def join_parts(cond, snapshot=None):
+    """``cond`` -> the parts [(pos, condition)] of one join query of pattern_batch_join (pos None: the link atom
+    itself), or HGXUnsupported.  Accepted: hg.apply(hg.targetAt(graph, i), c), or an And of those and of plain
+    sub-conditions; the plain sub-conditions together form one part without a projection.  Refused: a mapping
+    that is not a TargetAt (or one with a negative position), TargetAts of different snapshots or of another
+    one than ``snapshot``, a MapCondition nested inside a part, a BFSCondition, an Or of maps, and a condition
+    without any projection (that one is a plain pattern_batch_dnf query)."""
+    subs = [cond] if isinstance(cond, MapCondition) else _flatten(cond, []) if isinstance(cond, And) else None
+    if subs is None or not any(isinstance(c, MapCondition) for c in subs):
+        raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"not a projection or an And of projections: {cond!r}")
+    parts, rest = [], []
+    for c in subs:
+        if not isinstance(c, MapCondition):
+            _check_part(c, cond)
+            rest.append(c)
+            continue
+        m = c.mapping
+        if not isinstance(m, TargetAt) or m.pos < 0:
+            raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"mapping not accelerated: {m!r}")
+        if snapshot is None:
+            snapshot = m.snapshot
+        if not _same_store(m.snapshot, snapshot):
+            raise HGXUnsupported(_lib.HGX_E_UNSUPPORTED, "a targetAt of another snapshot")
+        _check_part(c.cond, cond)
+        parts.append((m.pos, c.cond))
+    if rest:
+        parts.append((None, rest[0] if len(rest) == 1 else And(rest)))
+    return parts
+
+
+def pattern_batch_join_arrays(snapshot, part_off, part_pos, clause_off, type_off, types, inc_off, inc, pos_off, pos,
+                              pset_off, pat_off, pat, arity, neg_off=None, term_off=None, lit_off=None, lit=None,
+                              ops=None, type_scan=False) -> QueryResult:
+    """Flat join batch for hgx_pattern_batch_join (include/hgx_join.h): join query j owns the parts
+    [part_off[j], part_off[j+1]); part s is query s of the pattern_batch_dnf_scan_arrays arrays that follow,
+    projected to target position part_pos[s] (-1: the link atom itself).  ``result.join`` holds the
+    statistics."""
+    part_off = np.ascontiguousarray(part_off, np.int64)
+    part_pos = np.ascontiguousarray(part_pos, np.int32)
+    clause_off = np.ascontiguousarray(clause_off, np.int64)
+    n = len(part_off) - 1
+    if neg_off is None:
+        neg_off = term_off = lit_off = np.zeros(0, np.int64)
+        lit = ops = np.zeros(0, np.int32)
+    arrs = [np.ascontiguousarray(type_off, np.int64), np.ascontiguousarray(types, np.int32),
+            np.ascontiguousarray(inc_off, np.int64), np.ascontiguousarray(inc, np.int32),
+            np.ascontiguousarray(pos_off, np.int64), np.ascontiguousarray(pos, np.int32),
+            np.ascontiguousarray(pset_off, np.int64), np.ascontiguousarray(pat_off, np.int64),
+            np.ascontiguousarray(pat, np.int32), np.ascontiguousarray(arity, np.int32),
+            np.ascontiguousarray(neg_off, np.int64), np.ascontiguousarray(term_off, np.int64),
+            np.ascontiguousarray(lit_off, np.int64), np.ascontiguousarray(lit, np.int32),
+            np.ascontiguousarray(ops, np.int32)]
+    h = C.c_void_p()
+    check(lib().hgx_pattern_batch_join(snapshot.handle, n, part_off.ctypes.data,
+                                       part_pos.ctypes.data if part_pos.size else None, clause_off.ctypes.data,
+                                       *(a.ctypes.data if a.size else None for a in arrs), len(arrs[-1]),
+                                       _lib.HGX_JOIN_TYPE_SCAN if type_scan else 0, C.byref(h)))
+    return _read_dnf_result(h, n, scan=True)
+
+
+def pattern_batch_join(snapshot, queries, type_scan=False) -> QueryResult:
+    """From links to the atoms they connect, in one device call: every query is a list of (pos, cond) parts
+    (pos None: the link atoms of cond themselves) or a condition join_parts lowers to one --
+    hg.apply(hg.targetAt(graph, pos), cond), or an And of those and of plain sub-conditions.  Each part's cond
+    (a condition, or a list of normalised clauses as pattern_batch_dnf takes) goes through to_dnf /
+    normalize_clause / split_type_scan exactly as in pattern_batch_dnf; its hits are projected to their target at
+    ``pos`` -- a link too short for it contributes nothing -- and the values of a query's parts are intersected
+    on the device: ascending, each atom once.  A query without parts is empty.  ``type_scan`` as in
+    pattern_batch_dnf (opt-in, the same rule).  ``result.join``: {"parts", "hits_projected", "values_distinct",
+    "kept", "ms_join", "bytes_join"} (hgx_query_result_join_stats); ``result.union`` / ``negation`` / ``scan``
+    describe the parts' evaluation."""
+    part_off, part_pos, clause_off, norm, negs = [0], [], [0], [], []
+    for q in queries:
+        for pos, cond in (q if type(q) in (list, tuple) else join_parts(q, snapshot)):
+            if pos is not None and pos < 0:
+                raise ValueError(f"bad target position {pos}")
+            part_pos.append(JOIN_SELF if pos is None else int(pos))
+            _lower_dnf_query(cond, type_scan, norm, negs)
+            clause_off.append(len(norm))
+        part_off.append(len(part_pos))
+    return pattern_batch_join_arrays(snapshot, part_off, part_pos, clause_off, *_ext_arrays(norm),
+                                     *(encode_negations(negs) if any(negs) else (None,) * 5), type_scan=type_scan)
+
+
 def pattern_batch_dnf(snapshot, queries, type_scan=False) -> QueryResult:
     """Evaluate many And / Or trees over the accelerated leaves in one device call: every query goes
     through to_dnf, its clauses run as one hgx_pattern_batch_ext-shaped batch and are united on the device
@@ -815,11 +946,7 @@ def pattern_batch_dnf(snapshot, queries, type_scan=False) -> QueryResult:
     statistics."""
     clause_off, norm, negs = [0], [], []
     for q in queries:
-        for c in (q if type(q) in (list, tuple) else [normalize_clause(c) for c in to_dnf(q)]):
-            c, ng = c if type(c) is tuple else (c, [])
-            for c1, ng1 in (split_type_scan(c, ng) if type_scan else [(c, ng)]):
-                norm.append(c1)
-                negs.append([] if c1 == "empty" else ng1)   # (an "empty" clause runs as a NOP: nothing to filter)
+        _lower_dnf_query(q, type_scan, norm, negs)
         clause_off.append(len(norm))
     if type_scan:
         return pattern_batch_dnf_scan_arrays(snapshot, clause_off, *_ext_arrays(norm),
@@ -926,6 +1053,31 @@ class GpuScanToQuery:
         return QueryMetaData(True, True, -1)
 
 
+class GpuMapToQuery:
+    """ConditionToQuery for MapCondition, registered with HGQueryConfiguration.addCompiler(MapCondition, ...):
+    hg.apply(hg.targetAt(graph, i), cond) as one device join batch (include/hgx_join.h).  getMetaData reports
+    ordered and random-access, which the result is (the sorted set of the projected atoms); the reference's
+    MapCondition translator reports neither (ToQueryMap.java:417-426: its ResultMapQuery delivers the values
+    in the inner order, duplicates included)."""
+
+    def getQuery(self, snapshot, cond):
+        parts = join_parts(cond, snapshot)
+
+        class _Q:
+            def execute(_self):
+                return list(pattern_batch_join(snapshot, [parts])[0].tolist())
+
+        return _Q()
+
+    def getMetaData(self, snapshot, cond):
+        try:
+            for _, c in join_parts(cond, snapshot):
+                to_dnf(c)
+        except HGXUnsupported:
+            return QueryMetaData(False, False, -1)
+        return QueryMetaData(True, True, -1)
+
+
 class HGQueryConfiguration:
     """Per-graph compiler registry (C/query/HGQueryConfiguration.java:37-66)."""
 
@@ -947,6 +1099,15 @@ def _has_not(cond):
     return isinstance(cond, Not) or (isinstance(cond, (And, Or)) and any(_has_not(c) for c in cond))
 
 
+def _find_all_join(snapshot, cond):
+    """find_all's And of mapped sub-queries on the device (pattern_batch_join), or None when join_parts or
+    the engine refuses it (the caller keeps its host path)."""
+    try:
+        return list(pattern_batch_join(snapshot, [join_parts(cond, snapshot)])[0].tolist())
+    except HGXUnsupported:
+        return None
+
+
 def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
     """hg.findAll(graph, cond) for the accelerated shapes."""
     if isinstance(cond, BFSCondition):
@@ -956,6 +1117,11 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
         seq = bfs_sequence(snapshot, [cond.start], cond.max_distance, gen)
         return seq.pairs(0)[1].tolist()
     if isinstance(cond, MapCondition):
+        compiler = (config.compiler(MapCondition) if config else None) or GpuMapToQuery()
+        try:
+            return compiler.getQuery(snapshot, cond).execute()
+        except HGXUnsupported:
+            pass   # a mapping or an inner condition the join does not take: the host path below
         return sorted({v for v in (cond.mapping(x) for x in find_all(snapshot, cond.cond, config)) if v is not None})
     if isinstance(cond, Or) or (isinstance(cond, And) and _has_or(cond)) or _has_not(cond):
         compiler = (config.compiler(Or) if config else None) or GpuOrToQuery()
@@ -967,6 +1133,9 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
             # a part the pattern engine does not take (Map / BFS sub-conditions): host set algebra
         if isinstance(cond, Or):
             return sorted(set().union(*(find_all(snapshot, c, config) for c in cond)))
+        joined = _find_all_join(snapshot, cond)
+        if joined is not None:
+            return joined
         subs = _flatten(cond, [])
         own = (MapCondition, BFSCondition, Or)
         sets = [set(find_all(snapshot, c, config)) for c in subs if isinstance(c, own)]
@@ -977,7 +1146,11 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
     if isinstance(cond, And):
         subs = _flatten(cond, [])
         if any(isinstance(c, (MapCondition, BFSCondition)) for c in subs):
-            # And of mapped / traversal sub-queries: set intersection of the parts
+            # And of mapped / traversal sub-queries: one device join batch when every part is a projection or
+            # plain, else set intersection of the parts
+            joined = _find_all_join(snapshot, cond)
+            if joined is not None:
+                return joined
             sets = [set(find_all(snapshot, c, config)) for c in subs if isinstance(c, (MapCondition, BFSCondition))]
             rest = [c for c in subs if not isinstance(c, (MapCondition, BFSCondition))]
             if rest:
