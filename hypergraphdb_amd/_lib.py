@@ -58,6 +58,7 @@ HGX_OPT_SP_BUDGET = 22   # include/hgx_paths.h
 HGX_OPT_COUNT_FUSED = 23
 HGX_OPT_NF_PULL = 24
 HGX_OPT_NF_HINT = 25
+HGX_OPT_HUB_MASK = 26   # value = mode + (T << 8) + (schedule << 16)
 HGX_NO_GOAL = -1
 
 # Every symbol include/hgx.h declares (checked by tests/test_abi.py without a GPU).
@@ -138,7 +139,8 @@ class BfsStats(C.Structure):
                 ("level_xtrips", C.c_int32 * 64), ("ms_block", C.c_double), ("bytes_block", C.c_double),
                 ("block_seeds", C.c_int64), ("block_rerun", C.c_int64), ("ms_coop", C.c_double),
                 ("bytes_coop", C.c_double), ("block_coop", C.c_int64), ("coop_fallbacks", C.c_int64),
-                ("count_pass_levels", C.c_int64), ("nf_hint_atoms", C.c_int64)]
+                ("count_pass_levels", C.c_int64), ("nf_hint_atoms", C.c_int64),
+                ("hub_mask_entries", C.c_int64), ("hub_mask_skipped", C.c_int64)]
 
     def as_dict(self):
         d = {"n_levels_expanded": self.n_levels_expanded, "n_batches": self.n_batches, "ms_total": self.ms_total,
@@ -146,7 +148,8 @@ class BfsStats(C.Structure):
              "ms_exchange": self.ms_exchange, "bytes_exchanged": self.bytes_exchanged, "bytes_min": self.bytes_min,
              "block_seeds": int(self.block_seeds), "block_rerun": int(self.block_rerun),
              "block_coop": int(self.block_coop), "coop_fallbacks": int(self.coop_fallbacks),
-             "count_pass_levels": int(self.count_pass_levels), "nf_hint_atoms": int(self.nf_hint_atoms)}
+             "count_pass_levels": int(self.count_pass_levels), "nf_hint_atoms": int(self.nf_hint_atoms),
+             "hub_mask_entries": int(self.hub_mask_entries), "hub_mask_skipped": int(self.hub_mask_skipped)}
         d["kernels"] = {k: {"ms": self.ms_kernel[i], "launches": int(self.launches[i]),
                             "bytes": self.bytes_kernel[i]} for i, k in enumerate(KERNELS)}
         if self.block_seeds or self.block_rerun:   # the workgroup-per-seed stage: one launch per 4096 seeds

@@ -658,13 +658,18 @@ __global__ void __launch_bounds__(256) hgx_atom_pull(int64_t A, const int64_t* _
 // loads in flight per lane at each stage.  Tiles with no work (e.g. the link atoms' zero-degree
 // rows) cost one load.
 // ---------------------------------------------------------------------------------------------
-template <int W, bool WRITE_LF>
+// FR (hub-mask levels): with fr_on the gather probes hgx_hub_mask's two-bit map ff instead
+// of the frontier bitmap and stores lr[tile] as it stores la[tile]: bit L set iff link L is active and holds an
+// fr atom (the targets past the first G of a long link included).
+template <int W, bool WRITE_LF, bool FR = false>
 __device__ __forceinline__ void gather2_body(int64_t M, const int64_t* __restrict__ tgt_off,
                                              const int32_t* __restrict__ tgt_idx,
                                              const int32_t* __restrict__ link_type, int32_t want_type,
                                              const u64* __restrict__ fa, const u64* __restrict__ full,
                                              const u64* __restrict__ lvl, u64* __restrict__ lf,
-                                             u64* __restrict__ la, u64* __restrict__ ctr, FullMask fm, int flags) {
+                                             u64* __restrict__ la, u64* __restrict__ ctr, FullMask fm, int flags,
+                                             const u64* __restrict__ ff = nullptr, u64* __restrict__ lr = nullptr,
+                                             bool fr_on = false) {
     constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G, PW = Lay<W>::PER_WAVE;
     static_assert(G >= 4, "gather2 needs G >= 4");
     typedef Vec<WPL> V;
@@ -693,19 +698,27 @@ __device__ __forceinline__ void gather2_body(int64_t M, const int64_t* __restric
             n[j] = __shfl(nme, j * PW + g);
             v[j] = sub < n[j] ? ld_col(tgt_idx + bb[j] + sub, nt_idx) : -1;
         }
-        unsigned pa = 0, pnf = 0;
+        unsigned pa = 0, pnf = 0, pfr = 0;
 #pragma unroll
         for (int j = 0; j < G; ++j)
             if (v[j] >= 0) {
-                if (bit(fa, v[j])) pa |= 1u << j;
+                if (FR && fr_on) {   // one probe of the two-bit map for the frontier bit and the fr bit
+                    const unsigned two = (unsigned)(ff[v[j] >> 5] >> ((v[j] & 31) * 2)) & 3u;
+                    pa |= (two & 1u) << j;
+                    pfr |= (two >> 1) << j;
+                } else if (bit(fa, v[j])) {
+                    pa |= 1u << j;
+                }
                 if (!skip_full || !bit(full, v[j])) pnf |= 1u << j;
             }
-        u64 word = 0;
+        u64 word = 0, word_r = 0;
 #pragma unroll
         for (int j = 0; j < G; ++j) {
             const int64_t L = tile * 64 + j * PW + g;
             unsigned ga = (unsigned)((__ballot((pa >> j) & 1u) >> base) & gmask);
             const bool any_nf0 = ((__ballot((pnf >> j) & 1u) >> base) & gmask) != 0ull;
+            bool any_fr = false;
+            if constexpr (FR) any_fr = ((__ballot((pfr >> j) & 1u) >> base) & gmask) != 0ull;
             typename V::T acc = V::zero();
             int nact = 0;
             bool act = false;
@@ -746,6 +759,13 @@ __device__ __forceinline__ void gather2_body(int64_t M, const int64_t* __restric
                     if (early && p + G < e && group_all<G>(V::eq(acc, FULL))) break;
                 }
                 act = nact > 0 && any_not_full;
+                if constexpr (FR) {
+                    for (int64_t p = b; p < e && fr_on && !any_fr; p += G) {   // group-uniform
+                        const int64_t q = p + sub;
+                        const int32_t myv = q < e ? tgt_idx[q] : -1;
+                        any_fr = ((__ballot(myv >= 0 && ((ff[myv >> 5] >> ((myv & 31) * 2 + 1)) & 1ull)) >> base) & gmask) != 0ull;
+                    }
+                }
             }
             if (act) {
                 if (WRITE_LF) st_row<V>(lf + L * W + sub * WPL, acc, nt_lf);
@@ -757,8 +777,11 @@ __device__ __forceinline__ void gather2_body(int64_t M, const int64_t* __restric
                 st_row<V>(lf + L * W + sub * WPL, V::zero(), nt_lf);   // the pull reads every row unprobed
             }
             word |= compress_groups<G>(__ballot(act), j * PW);
+            if constexpr (FR) word_r |= compress_groups<G>(__ballot(act && any_fr), j * PW);
         }
         if (lane == 0) la[tile] = word;
+        if constexpr (FR)
+            if (lane == 0) lr[tile] = word_r;
     }
     wave_add_sh(ctr + cActiveLinks, n_links);
     wave_add_sh(ctr + cActivePins, n_pins);
@@ -1123,6 +1146,244 @@ __global__ void __launch_bounds__(256) hgx_hub_finalize(int64_t H, const int32_t
     wave_add_sh(ctr + cNewDeg, n_newdeg);
     wave_add_sh(ctr + cNewDegNF, n_newdeg_nf);
     if (cpart) fuse_store<W>(cplanes, &cdone, cpart);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hub mask (HGX_OPT_HUB_MASK).  At an early dense level no hub is ever covered by
+// every traversal, because a few rare sources reach it through one or two links only; the hub pull then
+// reads one lf row per hub incidence entry.  C = the OR of the level rows of the snapshot's T
+// highest-degree atoms that are on the frontier holds most sources, and a hub chunk meets those atoms
+// within its first few hundred links.  Once the workgroup's accumulator covers C, a further lf row
+// matters only if it can hold a source outside C, i.e. if its link holds a frontier atom whose row has
+// a bit outside C (an `fr` atom).  hgx_hub_mask makes C and marks the fr atoms, the gather marks the links
+// that hold an fr atom in lr, and hgx_atom_pull_hub reads, after its chunk covers C, only the rows of
+// the links marked in lr.
+//
+// A hub-mask slot (kHmSlot words, zero before its level): the listed atoms on the frontier, |C|, and the
+// degree sum of the fr atoms (sharded like the statistics).  The kernels of the level evaluate the level
+// rule from the slot themselves, so the host never waits for it.
+// ---------------------------------------------------------------------------------------------
+constexpr int kHmListed = 0, kHmPop = 1, kHmDeg = 2;
+constexpr int kHmSlot = kStatShards * kStatStride;
+constexpr int kHubTop = 64;   // atoms in the snapshot's top list (T <= kHubTop)
+
+// mode 2 = every level with a listed atom on its frontier; 1 = also |C| >= S / 2 and the fr atoms'
+// degree sum below deg_limit (a quarter of the hub incidence)
+__device__ __forceinline__ bool hub_mask_on(const u64* __restrict__ hm, int mode, int S, u64 deg_limit) {
+    if (hm[kHmListed] == 0ull) return false;
+    if (mode == 2) return true;
+    if (2ull * hm[kHmPop] < (u64)S) return false;
+    u64 d = 0;
+    for (int k = 0; k < kStatShards; ++k) d += hm[k * kStatStride + kHmDeg];
+    return d < deg_limit;
+}
+
+// Every workgroup ORs the rows of the listed frontier atoms into its own copy of C (at most kHubTop rows
+// from L2), workgroup 0 stores C and its statistics and clears the other slot for the next eligible level.
+// Then a thread per frontier word tests the rows of the word's atoms against C and stores the word's 128 bits of
+// ff whole: two bits an atom, bit 0 = on the frontier, bit 1 = an fr atom (a frontier atom whose row has a bit
+// outside C), so the gather's one probe of a target tells both.
+__device__ __forceinline__ u64 spread_bits(uint32_t v) {   // bit i of v to bit 2 i
+    u64 x = v;
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+template <int W>
+__global__ void __launch_bounds__(256) hgx_hub_mask(int64_t A, const int32_t* __restrict__ top, int n_top,
+                                                    const u64* __restrict__ fa, const u64* __restrict__ lvl,
+                                                    const int64_t* __restrict__ inc_off, u64* __restrict__ crow,
+                                                    u64* __restrict__ ff, u64* __restrict__ hm,
+                                                    u64* __restrict__ hm_next) {
+    static_assert(W >= 8 && kHmSlot == 256, "hgx_hub_mask: rows of >= 8 words, one thread per slot word");
+    __shared__ u64 sC[W];
+    __shared__ unsigned int s_listed;
+    if (threadIdx.x < W) sC[threadIdx.x] = 0ull;
+    if (threadIdx.x == 0) s_listed = 0u;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_top * W; i += 256) {
+        const int32_t a = top[i / W];
+        const int w = i % W;
+        if (bit(fa, a)) {
+            const u64 x = lvl[(int64_t)a * W + w];
+            if (x) atomicOr(&sC[w], x);
+            if (w == 0) atomicAdd(&s_listed, 1u);
+        }
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < W) crow[threadIdx.x] = sC[threadIdx.x];
+        if (threadIdx.x == 0) {
+            int pc = 0;
+            for (int w = 0; w < W; ++w) pc += __popcll(sC[w]);
+            hm[kHmListed] = s_listed;
+            hm[kHmPop] = (u64)pc;
+        }
+        hm_next[threadIdx.x] = 0ull;
+    }
+    if (s_listed == 0u) return;   // block-uniform: the step is off this level, ff is not read
+    const int64_t nwords = (A + 63) >> 6;
+    const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nt = (int64_t)gridDim.x * blockDim.x;
+    u64 deg = 0;
+    for (int64_t wi = t0; wi < nwords; wi += nt) {   // a thread per frontier word (a sparse frontier: a bit or two)
+        const u64 x = fa[wi];
+        u64 f = 0;
+        for (u64 m = x; m; m &= m - 1ull) {
+            const int k = __ffsll((long long)m) - 1;
+            const int64_t u = wi * 64 + k;
+            if (u >= A) break;
+            const u64* row = lvl + u * W;
+            u64 o = 0;
+#pragma unroll
+            for (int w = 0; w < W; w += 2) {
+                const u64x2 r = *reinterpret_cast<const u64x2*>(row + w);
+                o |= (r.x & ~sC[w]) | (r.y & ~sC[w + 1]);
+            }
+            if (o) {
+                f |= 1ull << k;
+                deg += (u64)(inc_off[u + 1] - inc_off[u]);
+            }
+        }
+        *reinterpret_cast<u64x2*>(ff + 2 * wi) =
+            u64x2{spread_bits((uint32_t)x) | (spread_bits((uint32_t)f) << 1),
+                  spread_bits((uint32_t)(x >> 32)) | (spread_bits((uint32_t)(f >> 32)) << 1)};
+    }
+    block_add_sh(hm, kHmDeg, deg);
+}
+
+// The dense gather of a hub-mask level: hgx_link_gather2 with the lr word of every tile.
+template <int W>
+__global__ void __launch_bounds__(256) hgx_link_gather2_fr(int64_t M, const int64_t* __restrict__ tgt_off,
+                                                           const int32_t* __restrict__ tgt_idx,
+                                                           const int32_t* __restrict__ link_type, int32_t want_type,
+                                                           const u64* __restrict__ fa, const u64* __restrict__ full,
+                                                           const u64* __restrict__ lvl, u64* __restrict__ lf,
+                                                           u64* __restrict__ la, u64* __restrict__ ctr, FullMask fm,
+                                                           int flags, const u64* __restrict__ ff, u64* __restrict__ lr,
+                                                           const u64* __restrict__ hm, int mode, int S, u64 deg_limit) {
+    gather2_body<W, true, true>(M, tgt_off, tgt_idx, link_type, want_type, fa, full, lvl, lf, la, ctr, fm, flags, ff,
+                                lr, hub_mask_on(hm, mode, S, deg_limit));
+}
+
+template <typename T>
+__device__ __forceinline__ T row_shfl_xor(T x, int off);
+template <>
+__device__ __forceinline__ u64 row_shfl_xor<u64>(u64 x, int off) {
+    return (u64)__shfl_xor((long long)x, off);
+}
+template <>
+__device__ __forceinline__ u64x2 row_shfl_xor<u64x2>(u64x2 x, int off) {
+    return u64x2{(u64)__shfl_xor((long long)x.x, off), (u64)__shfl_xor((long long)x.y, off)};
+}
+
+// The hub pull of a hub-mask level (symmetric mode, G >= 4, every lf row written).  With the step off
+// (hub_mask_on; block-uniform) it is hgx_atom_pull_heavy's walk.  With it on, the workgroup walks its chunk in
+// rounds of 256 entries, entry r * 256 + thread to the thread, so its accumulators meet the chunk's first
+// links together.  After the rounds whose bit is set in `sched` the waves OR their groups' accumulators by
+// shuffles (block-uniform control flow, every lane active), the four wave rows meet in LDS (two buffers, one
+// barrier a test) and every group tests the same row: (acc | vis[h] | ~C) == FULL switches the workgroup to
+// filtered mode, where an entry probes lr[L] first and loads lf[L] only when the bit is set.  Exact: a
+// source of C is already in acc | vis[h]; a source s outside C in lf[L] comes from a frontier atom of L
+// whose row holds s, which is an fr atom, so lr[L] is set and the row is read.
+// cCand / cNfRows (unused by a dense level) take the entries walked in filtered mode and the rows they skipped.
+template <int W>
+__global__ void __launch_bounds__(256) hgx_atom_pull_hub(const HeavyChunk* __restrict__ chunks,
+                                                         const int32_t* __restrict__ inc_row,
+                                                         const u64* __restrict__ la, const u64* __restrict__ lf,
+                                                         const u64* __restrict__ lr, const u64* __restrict__ crow,
+                                                         const u64* __restrict__ hm, const u64* __restrict__ vis,
+                                                         const u64* __restrict__ ever, const u64* __restrict__ full,
+                                                         u64* __restrict__ hubacc, u64* __restrict__ ctr, FullMask fm,
+                                                         int flags, int mode, int S, u64 deg_limit, unsigned sched) {
+    constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G;
+    constexpr int NG = 256 / G;
+    static_assert(G >= 4, "hgx_atom_pull_hub needs G >= 4");
+    typedef Vec<WPL> V;
+    __shared__ __attribute__((aligned(16))) u64 red[NG * W];   // step off: a row per group; on: [2][4][W] wave rows
+    const HeavyChunk c = chunks[blockIdx.x];
+    if ((flags & 4) && bit(full, c.atom)) return;   // block-uniform
+    const int sub = threadIdx.x & (G - 1);
+    const int gi = threadIdx.x / G;
+    const typename V::T FULL = full_part<W>(fm, sub);
+    const bool early = (flags & 2) != 0;
+    u64 n_inc = 0, n_vis = 0, n_filt = 0, n_skip = 0;
+    typename V::T acc = V::zero(), old = V::zero();
+    if (!hub_mask_on(hm, mode, S, deg_limit)) {   // block-uniform
+        const int64_t n = c.end - c.beg;
+        const int64_t per = (n + NG - 1) / NG;
+        const int64_t b = c.beg + gi * per;
+        const int64_t e = b + per < c.end ? b + per : c.end;
+        bool have_old = false;
+        if (b < e)
+            pull_range<W, kSym>(c.atom, b, e, inc_row, la, lf, nullptr, nullptr, nullptr, nullptr,
+                                vis + (int64_t)c.atom * W, bit(ever, c.atom), FULL, sub, acc, old, have_old, n_inc,
+                                n_vis, early);
+        V::st(red + gi * W + sub * WPL, acc);
+        __syncthreads();
+        for (int j = threadIdx.x; j < W; j += 256) {
+            u64 r = 0;
+            for (int k = 0; k < NG; ++k) r |= red[k * W + j];
+            if (r) atomicOr(hubacc + (int64_t)c.slot * W + j, r);
+        }
+    } else {
+        const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, base = lane & ~(G - 1);
+        const u64 gmask = (1ull << G) - 1ull;
+        if (bit(ever, c.atom)) old = V::ld(vis + (int64_t)c.atom * W + sub * WPL);
+        const typename V::T notc = ~V::ld(crow + sub * WPL);
+        bool filt = false;
+        int nt = 0;   // tests done: the LDS buffer of the next one is nt & 1
+        int rd = 0;
+        for (int64_t q0 = c.beg; q0 < c.end; q0 += 256, ++rd) {   // block-uniform
+            const int64_t q = q0 + threadIdx.x;
+            const int32_t myL = q < c.end ? inc_row[q] : -1;
+            bool mya = myL >= 0;
+            if (filt) {
+                const bool keep = mya && bit(lr, myL);
+                n_filt += mya;
+                n_skip += mya && !keep;
+                mya = keep;
+            }
+            const unsigned ga = (unsigned)((__ballot(mya) >> base) & gmask);
+            typename V::T r[G];
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                const int32_t Lk = __shfl(myL, base + k);
+                r[k] = ((ga >> k) & 1u) ? V::ld(lf + (int64_t)Lk * W + sub * WPL) : V::zero();
+            }
+#pragma unroll
+            for (int k = 0; k < G; ++k) acc |= r[k];
+            n_inc += __popc(ga);
+            if (filt || q0 + 256 >= c.end || !((sched >> (rd < 31 ? rd : 31)) & 1u)) continue;
+            typename V::T x = acc;
+#pragma unroll
+            for (int off = G; off < 64; off <<= 1) x |= row_shfl_xor<typename V::T>(x, off);
+            u64* buf = red + (nt & 1) * 4 * W;
+            ++nt;
+            if (lane < G) V::st(buf + wv * W + sub * WPL, x);
+            __syncthreads();
+            const typename V::T cov = V::ld(buf + sub * WPL) | V::ld(buf + W + sub * WPL) |
+                                      V::ld(buf + 2 * W + sub * WPL) | V::ld(buf + 3 * W + sub * WPL) | old;
+            if (early && group_all<G>(V::eq(cov, FULL))) break;   // every group tests the same row
+            filt = group_all<G>(V::eq((cov | notc) & FULL, FULL));
+        }
+        typename V::T x = acc;
+#pragma unroll
+        for (int off = G; off < 64; off <<= 1) x |= row_shfl_xor<typename V::T>(x, off);
+        u64* buf = red + (nt & 1) * 4 * W;
+        if (lane < G) V::st(buf + wv * W + sub * WPL, x);
+        __syncthreads();
+        for (int j = threadIdx.x; j < W; j += 256) {
+            const u64 r = buf[j] | buf[W + j] | buf[2 * W + j] | buf[3 * W + j];
+            if (r) atomicOr(hubacc + (int64_t)c.slot * W + j, r);
+        }
+    }
+    if (sub != 0) n_inc = 0;
+    wave_add_sh(ctr + cIncHeavy, n_inc);
+    wave_add_sh(ctr + cCand, n_filt);
+    wave_add_sh(ctr + cNfRows, n_skip);
 }
 
 // Sparse levels: mark every (typed) link incident to a frontier atom.  One wave per frontier word:
@@ -3874,7 +4135,7 @@ constexpr int kZeroLevels = 64;      // level counter blocks / count rows cleare
 
 // Up to kZeroParts device ranges cleared by one launch (a traversal's prologue cleared six buffers
 // with six fill launches, each a few microseconds of device time and a gap).
-constexpr int kZeroParts = 8;
+constexpr int kZeroParts = 10;
 struct ZeroSpans {
     u64* p[kZeroParts];
     int64_t n[kZeroParts];   // words
@@ -4009,6 +4270,49 @@ constexpr size_t kFcRecBudget = (size_t)16 << 30;
 // The snapshot's per-entry target records (hgx_fc_rec), built on first use on the root snapshot and
 // shared by its contexts; nullptr when over budget, when a quarter of the free device memory cannot
 // hold them, or when some link has more than 8 targets.  Caller holds g->mu.
+// The snapshot's top list (HGX_OPT_HUB_MASK): its kHubTop atoms of largest (degree, id), descending, built in
+// the stream on first use like nbr_hint.  Every hub outranks every light atom, so the hubs' degrees decide
+// when there are kHubTop hubs; a smaller snapshot sorts all its degrees.  Caller holds g->mu.
+void hub_top_list(hgx_graph* g, hipStream_t s) {
+    if (g->top_list) return;
+    std::vector<int32_t> ids;
+    std::vector<int64_t> deg;
+    if (g->n_heavy >= kHubTop) {
+        const int64_t nh = g->n_heavy;
+        ids.resize((size_t)nh);
+        deg.resize((size_t)nh);
+        int64_t* dd = (int64_t*)g->alloc(sizeof(int64_t) * (size_t)nh);
+        hgx_fc_deg<<<grid_for(nh, 256, 4096), 256, 0, s>>>(nh, g->heavy_atom, g->inc_off, dd);
+        HGX_CHECK_LAUNCH();
+        HGX_HIP(hipMemcpyAsync(ids.data(), g->heavy_atom, sizeof(int32_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
+        HGX_HIP(hipMemcpyAsync(deg.data(), dd, sizeof(int64_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
+        HGX_HIP(hipStreamSynchronize(s));
+        g->release(dd, sizeof(int64_t) * (size_t)nh);
+    } else {
+        std::vector<int64_t> off((size_t)g->A + 1);
+        HGX_HIP(hipMemcpyAsync(off.data(), g->inc_off, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost, s));
+        HGX_HIP(hipStreamSynchronize(s));
+        ids.resize((size_t)g->A);
+        deg.resize((size_t)g->A);
+        for (int64_t a = 0; a < g->A; ++a) {
+            ids[(size_t)a] = (int32_t)a;
+            deg[(size_t)a] = off[(size_t)a + 1] - off[(size_t)a];
+        }
+    }
+    std::vector<int64_t> ord(ids.size());
+    for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int64_t)k;
+    const size_t keep = std::min<size_t>(ord.size(), (size_t)kHubTop);
+    std::partial_sort(ord.begin(), ord.begin() + (int64_t)keep, ord.end(), [&](int64_t a, int64_t b) {
+        return deg[(size_t)a] != deg[(size_t)b] ? deg[(size_t)a] > deg[(size_t)b] : ids[(size_t)a] > ids[(size_t)b];
+    });
+    int32_t top[kHubTop] = {0};
+    for (size_t k = 0; k < keep; ++k) top[k] = ids[(size_t)ord[k]];
+    HGX_HIP(hipMalloc(&g->top_list, sizeof(int32_t) * kHubTop));
+    HGX_HIP(hipMemcpyAsync(g->top_list, top, sizeof(top), hipMemcpyHostToDevice, s));
+    HGX_HIP(hipStreamSynchronize(s));   // `top` is on this frame
+    g->top_n = (int32_t)keep;
+}
+
 const int4* fc_records(hgx_graph* g, hipStream_t s) {
     hgx_graph* root = g->base ? g->base : g;
     std::lock_guard<std::mutex> lk(root->ylist_mu);
@@ -4493,6 +4797,16 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
     u64* ever = (u64*)g->alloc(bm_bytes);
     u64* full = (u64*)g->alloc(bm_bytes);
     u64* la = (u64*)g->alloc(la_bytes);
+    // hub mask (HGX_OPT_HUB_MASK): the two-bit map ff, the links' lr bits, C's row and two rule slots (alternating
+    // over the levels that run the step; both zero after the prologue, then each level clears the other's)
+    bool hm_ok = false;
+    if constexpr (MODE == kSym && Lay<W>::G >= 4)
+        hm_ok = g->hub_mask != 0 && !tr && !g->shard && g->n_chunks > 0;
+    const size_t hm_bytes = sizeof(u64) * (2 * kHmSlot + 16);
+    u64* hm = hm_ok ? (u64*)g->alloc(hm_bytes) : nullptr;   // [2][kHmSlot] slots, then C's row
+    u64* hm_fr = hm_ok ? (u64*)g->alloc(2 * bm_bytes) : nullptr;   // ff: two bits an atom
+    u64* hm_lr = hm_ok ? (u64*)g->alloc(la_bytes) : nullptr;
+    int hm_levels = 0;
     const int max_levels_cap = 4096;
     u64* ctr = (u64*)g->alloc(sizeof(u64) * kCtrBlock * max_levels_cap);
     int32_t* d_atoms = (int32_t*)g->alloc(sizeof(int32_t) * seed_atoms.size());
@@ -4523,6 +4837,7 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
     z.add(full, bm_bytes);
     z.add(bt.fa[0], bm_bytes);
     z.add(hubacc, sizeof(u64) * (size_t)std::max<int64_t>(g->n_heavy, 1) * W);
+    if (hm) z.add(hm, hm_bytes);
     z.add(ctr, sizeof(u64) * kCtrBlock * kZeroLevels);
     z.add(ctr + (size_t)(max_levels_cap - 1) * kCtrBlock, sizeof(u64) * kCtrBlock);   // scratch slots
     if (!tr) {   // per-source counts of push levels, accumulated by their finalise (readout without a pass)
@@ -5057,9 +5372,51 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         // gather then writes a (zero) row for every link and the pull reads rows without probing la
         // -- one dependent load fewer per incidence chunk (HGX_OPT_BFS_FLAGS bit 7).
         if (v2 && (lflags & 128) && MODE == kSym && push_volume_nf >= 2 * (u64)M) lflags |= kAllRows;
+        // hub mask: an all-rows level of the MLP kernels; C, fr and the rule's counters first (the frontier is final)
+        bool hmask = false;
+        u64* hm_slot = nullptr;
+        u64 hm_limit = 0;
+        int hm_S = 0;
+        if constexpr (MODE == kSym && Lay<W>::G >= 4) {
+            // (hgx_hub_mask reads every frontier row: under the rule only while the frontier is at most half of the atoms)
+            hmask = hm_ok && v2 && (lflags & kAllRows) && !(lflags & (kGatherO5 | kHeavyMlp2)) &&
+                    (g->hub_mask == 2 || front_atoms * 2 <= (u64)A);
+            if (hmask) {
+                hub_top_list(g, s);   // once per snapshot
+                hm_slot = hm + (size_t)(hm_levels & 1) * kHmSlot;
+                hm_limit = (u64)(g->I_heavy / 4);
+                hm_S = (int)bt.S;
+                Events e0 = tm.start(kKindGather, d);
+                hgx_hub_mask<W><<<grid_for(ceil_div(A, 64), 256, 2048), 256, 0, s>>>(
+                    A, g->top_list, std::min(g->hub_mask_t, g->top_n), fa, lvl, g->inc_off, hm + 2 * kHmSlot, hm_fr,
+                    hm_slot, hm + (size_t)((hm_levels + 1) & 1) * kHmSlot);
+                HGX_CHECK_LAUNCH();
+                tm.stop(e0);
+                ++hm_levels;
+                if (trace) {   // the rule's inputs (a host wait: tracing only)
+                    u64 h[kHmSlot + 16];
+                    HGX_HIP(hipMemcpyAsync(h, hm_slot, sizeof(u64) * kHmSlot, hipMemcpyDeviceToHost, s));
+                    HGX_HIP(hipMemcpyAsync(h + kHmSlot, hm + 2 * kHmSlot, sizeof(u64) * 16, hipMemcpyDeviceToHost, s));
+                    HGX_HIP(hipStreamSynchronize(s));
+                    u64 fdeg = 0, pc = 0;
+                    for (int k = 0; k < kStatShards; ++k) fdeg += h[k * kStatStride + kHmDeg];
+                    for (int w = 0; w < W; ++w) pc += (u64)__builtin_popcountll(h[kHmSlot + w]);
+                    std::fprintf(stderr, "[hgx bfs] level %d hub mask: T %d listed on the frontier %llu |C| %llu (row %llu) "
+                                 "fr degree sum %llu limit %llu\n", d, std::min(g->hub_mask_t, g->top_n),
+                                 (unsigned long long)h[kHmListed], (unsigned long long)h[kHmPop], (unsigned long long)pc,
+                                 (unsigned long long)fdeg, (unsigned long long)hm_limit);
+                }
+            }
+        }
         Events e1 = tm.start(kKindGather, d);
+        if constexpr (MODE == kSym && Lay<W>::G >= 4) {
+            if (hmask)
+                hgx_link_gather2_fr<W><<<gather_grid, block, 0, s>>>(
+                    M, g->tgt_off, g->tgt_idx, g->link_type, want_type, fa, full, lvl, lf, la, c, fm, lflags, hm_fr,
+                    hm_lr, hm_slot, g->hub_mask, hm_S, hm_limit);
+        }
         if constexpr (Lay<W>::G >= 4) {
-            if (v2)
+            if (v2 && !hmask)
             {
                 if (lflags & kGatherO5)   // diagnostic A/B (bit 10)
                     hgx_link_gather2_o5<W, MODE == kSym><<<gather_grid, block, 0, s>>>(
@@ -5122,6 +5479,13 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         tm.stop(e2);
         if (g->n_chunks > 0) {
             Events e3 = tm.start(kKindHeavy, d);
+            if constexpr (MODE == kSym && Lay<W>::G >= 4) {
+                if (hmask)
+                    hgx_atom_pull_hub<W><<<(unsigned)g->n_chunks, block, 0, s>>>(
+                        g->chunks, g->inc_row, la, lf, hm_lr, hm + 2 * kHmSlot, hm_slot, vis, ever, full, hubacc, c, fm,
+                        lflags, g->hub_mask, hm_S, hm_limit, g->hub_mask_sched);
+            }
+            if (!hmask)
             hgx_atom_pull_heavy<W, MODE><<<(unsigned)g->n_chunks, block, 0, s>>>(
                     g->chunks, g->inc_row, la, lf, g->tgt_off, g->tgt_idx, fa, lvl, vis, ever, full, hubacc, c, fm,
                     lflags, cd);
@@ -5216,6 +5580,11 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
     g->release(ever, bm_bytes);
     g->release(full, bm_bytes);
     g->release(la, la_bytes);
+    if (hm) {
+        g->release(hm, hm_bytes);
+        g->release(hm_fr, 2 * bm_bytes);
+        g->release(hm_lr, la_bytes);
+    }
     if (lcand) g->release(lcand, la_bytes);
     if (cand) g->release(cand, bm_bytes);
     if (flist) g->release(flist, flist_bytes);
@@ -5731,6 +6100,10 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
                 r->stats.bytes_kernel[HGX_K_HUB_FINALIZE] += b_hub;
                 r->stats.launches[heavy_kind] += 1;
                 r->stats.launches[HGX_K_HUB_FINALIZE] += 1;
+            }
+            if (c[cDirRows] == 0) {   // dense gather + pull: the hub-mask pull's two counters
+                r->stats.hub_mask_entries += (int64_t)c[cCand];
+                r->stats.hub_mask_skipped += (int64_t)c[cNfRows];
             }
             if (d < 64) {
                 for (int k = 0; k < 8; ++k) r->stats.level_rows[d][k] += (int64_t)c[k];

@@ -458,6 +458,9 @@ int hgx_graph_update(hgx_graph* g, int64_t num_atoms, int64_t n_add, const int32
     g->hasinc = nullptr;
     if (g->nbr_hint) (void)hipFree(g->nbr_hint);
     g->nbr_hint = nullptr;
+    if (g->top_list) (void)hipFree(g->top_list);
+    g->top_list = nullptr;
+    g->top_n = 0;
     if (g->inc_yf) (void)hipFree(g->inc_yf);
     g->inc_yf = nullptr;
     free_yield_lists(g);

@@ -39,7 +39,7 @@ void graph_release(hgx_graph* g) {
     HGX_FREE_OWN(link_atom); HGX_FREE_OWN(tgt_off); HGX_FREE_OWN(tgt_idx); HGX_FREE_OWN(link_type);
     HGX_FREE_OWN(inc_off); HGX_FREE_OWN(inc_row); HGX_FREE_OWN(inc_type); HGX_FREE_OWN(inc_ts_row);
     HGX_FREE_OWN(inc_ts_type); HGX_FREE_OWN(inc_ts_tgt); HGX_FREE_OWN(heavy_atom); HGX_FREE_OWN(chunks);
-    HGX_FREE_OWN(hasinc); HGX_FREE_OWN(nbr_hint); HGX_FREE_OWN(inc_yf); HGX_FREE_OWN(pchunks); HGX_FREE_OWN(type_idx);
+    HGX_FREE_OWN(hasinc); HGX_FREE_OWN(nbr_hint); HGX_FREE_OWN(top_list); HGX_FREE_OWN(inc_yf); HGX_FREE_OWN(pchunks); HGX_FREE_OWN(type_idx);
 #undef HGX_FREE_OWN
     if (g->zacc) (void)hipFree(g->zacc);
     if (g->q_ticket) (void)hipFree(g->q_ticket);
@@ -314,7 +314,7 @@ int hgx_graph_context(hgx_graph* g, hgx_graph** out) {
     c->inc_ts_row = g->inc_ts_row; c->inc_ts_type = g->inc_ts_type; c->inc_ts_tgt = g->inc_ts_tgt;
     c->n_heavy = g->n_heavy; c->I_heavy = g->I_heavy; c->n_chunks = g->n_chunks;
     c->heavy_atom = g->heavy_atom; c->chunks = g->chunks;
-    c->hasinc = g->hasinc; c->nbr_hint = g->nbr_hint; c->inc_yf = g->inc_yf; c->pchunks = g->pchunks; c->n_pchunks = g->n_pchunks;
+    c->hasinc = g->hasinc; c->nbr_hint = g->nbr_hint; c->top_list = g->top_list; c->top_n = g->top_n; c->inc_yf = g->inc_yf; c->pchunks = g->pchunks; c->n_pchunks = g->n_pchunks;
     c->max_arity = g->max_arity; c->max_deg = g->max_deg;
     // the snapshot's options at this point (set separately on the context afterwards)
     c->timing = g->timing; c->bfs_flags = g->bfs_flags; c->seq_budget_bytes = g->seq_budget_bytes;
@@ -331,6 +331,7 @@ int hgx_graph_context(hgx_graph* g, hgx_graph** out) {
     c->count_fused = g->count_fused;
     c->nf_pull = g->nf_pull;
     c->nf_hint = g->nf_hint;
+    c->hub_mask = g->hub_mask; c->hub_mask_t = g->hub_mask_t; c->hub_mask_sched = g->hub_mask_sched;
     c->ranks_ordered = g->ranks_ordered; c->q_inline = g->q_inline;
     c->q_coalesce = g->q_coalesce; c->q_coalesce_max = g->q_coalesce_max;
     guard.c = nullptr;
@@ -593,6 +594,14 @@ int hgx_set_option(hgx_graph* g, int32_t option, int64_t value) {
     } else if (option == HGX_OPT_NF_HINT) {
         if (value != 0 && value != 1) fail(HGX_E_INVALID, "hgx_set_option: HGX_OPT_NF_HINT is 0 or 1");
         g->nf_hint = (int32_t)value;
+    } else if (option == HGX_OPT_HUB_MASK) {
+        // bits 0-1 the mode, bits 8-14 T (0 = the default), bits 16-31 the test schedule (0 = the default)
+        const int64_t mode = value & 0xff, t = (value >> 8) & 0xff, sched = (value >> 16) & 0xffff;
+        if (value < 0 || (value >> 32) != 0 || mode > 2 || t > 64)
+            fail(HGX_E_INVALID, "hgx_set_option: HGX_OPT_HUB_MASK is 0, 1 or 2 (+ T << 8, T <= 64, + schedule << 16)");
+        g->hub_mask = (int32_t)mode;
+        g->hub_mask_t = t ? (int32_t)t : 32;
+        g->hub_mask_sched = sched ? (uint32_t)sched : 0x8Bu;
     } else fail(HGX_E_INVALID, "hgx_set_option: unknown option");
     HGX_API_END
 }

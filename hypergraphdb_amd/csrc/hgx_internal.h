@@ -294,6 +294,9 @@ struct hgx_graph {
     int32_t count_fused = 1;                        // HGX_OPT_COUNT_FUSED: dense-level kernels count the rows they store
     int32_t nf_pull = 1;                            // HGX_OPT_NF_PULL: 0 = late levels only, 8-entry step; 1 = the rule; 2 = every eligible level
     int32_t nf_hint = 1;                            // HGX_OPT_NF_HINT: direct-pull levels try the listed atoms' hint rows first
+    int32_t hub_mask = 1;                           // HGX_OPT_HUB_MASK: 0 = off, 1 = the level rule, 2 = every eligible level;
+    int32_t hub_mask_t = 32;                        //   atoms of the top list ORed into C (1 .. 64);
+    uint32_t hub_mask_sched = 0x8Bu;                //   bit r: the hub pull tests its cover after round r of 256 entries
     unsigned long long* co_vis = nullptr;           // multi-workgroup stage: per-seed visited bitmaps (zero between calls)
     unsigned long long* sc_tab = nullptr;           // order-exact grid stage: level hash, word / key counts (empty between calls)
     int64_t co_vis_seeds = 0, co_pcap = 0;          //   seeds they hold; pair-list capacity (grown on demand)
@@ -319,6 +322,8 @@ struct hgx_graph {
     uint64_t* hasinc = nullptr;          // [A/64 + 1] bit set <=> inc(atom) non-empty (non-full pull levels)
     int32_t* nbr_hint = nullptr;         // [A] the co-target of largest (degree, id) over the atom's links, -1 = none
                                          //   (HGX_OPT_NF_HINT: direct-pull levels, made on first use)
+    int32_t* top_list = nullptr;         // [top_n <= 64] the atoms of largest (degree, id), descending
+    int32_t top_n = 0;                   //   (HGX_OPT_HUB_MASK: dense levels, made on first use)
     uint8_t* inc_yf = nullptr;           // [I] ordered-mode yield flags per incidence (frontier push), made on first use
     hgx::HeavyChunk* pchunks = nullptr;  // frontier push: kPushChunk-entry chunks of atoms with deg > kPushLight
     int64_t n_pchunks = -1;              // -1 = not built yet

@@ -161,6 +161,10 @@ typedef struct hgx_bfs_stats {
     /* listed atoms of the direct-pull levels (summed over levels and batches) whose row was decided by their
      * hint neighbour's frontier row, without a walk over their incidence (HGX_OPT_NF_HINT) */
     int64_t nf_hint_atoms;
+    /* hub incidence entries of the dense levels (summed over levels and batches) walked after their chunk
+     * covered the top atoms' sources, and the link rows those entries did not read (HGX_OPT_HUB_MASK) */
+    int64_t hub_mask_entries;
+    int64_t hub_mask_skipped;
 } hgx_bfs_stats;
 
 const char *hgx_version(void);
@@ -565,6 +569,18 @@ int  hgx_shard_graph_create(const hgx_shard *s, int32_t device, hgx_graph **out)
  * 0 = every listed atom walks its incidence.  The results are the same for both values;
  * hgx_bfs_stats.nf_hint_atoms counts the atoms the hint decided. */
 #define HGX_OPT_NF_HINT      25
+/* HGX_OPT_HUB_MASK (default 1): a dense gather + pull level of hgx_bfs_batch on a whole snapshot, symmetric
+ * generator, more than 256 seeds in a batch, every link row written: C = the OR of the level rows of the
+ * snapshot's T atoms of largest (degree, id) that are on the frontier (the list is built on first use and
+ * dropped by hgx_graph_update).  A hub chunk whose accumulator covers C goes on reading only the rows of the
+ * links that hold a frontier atom with a source outside C (hgx_hub_mask, hgx_atom_pull_hub).
+ * 0 = off; 1 = on the levels where a listed atom is on the frontier, C holds half of the sources and those
+ * frontier atoms hold under a quarter of the hub incidence; 2 = every eligible level with a listed atom on
+ * the frontier (tests, A/B).  value = mode + (T << 8) + (schedule << 16): T = 1 .. 64 (0 = the default, 32);
+ * bit r of the schedule = the hub pull tests its cover after round r of 256 entries (0 = the default, 0x8B).
+ * The results are the same for every value; hgx_bfs_stats.hub_mask_entries counts the hub entries walked
+ * after a chunk covered C, hub_mask_skipped the link rows they did not read. */
+#define HGX_OPT_HUB_MASK     26
 /* Coalescing statistics of a graph since its creation: device batches run by the packed pattern path
  * and caller batches they served (caller / device = the mean coalescing factor). */
 int  hgx_query_coalesce_stats(hgx_graph *g, int64_t *device_batches, int64_t *caller_batches);

@@ -6,6 +6,8 @@
  * any pull reads -- light atoms and hubs apart.  Item 13's hint columns follow: how concentrated the
  * neighbour hints are, and per level the listed atoms that vis | lvl[hint] covers (with one hint, with a
  * second), and the entry walk left to the atoms they do not cover, per exit step.
+ * Item 14's hub-mask columns: per level and T = 8/16/32/64, |C|, the fr atoms and their degree sum, the links
+ * with an fr atom, the hub entries walked until a chunk's block-wide test passes and the lr-set share after it.
  *   gcc -O3 -fopenmp -o bfs_level_model tools/bfs_level_model.c hypergraphdb_amd/csrc/hgx_gen.c -lm
  *   ./bfs_level_model [scale=0.01] [sources=1024] [depth=4] [nodes=10e6*scale] [links=40e6*scale]   */
 #include <stdint.h>
@@ -20,6 +22,8 @@ int hgx_gen_sources(int64_t n, int64_t P, const int32_t *tgt_idx, int64_t k, uin
 
 enum { NE = 5, HEAVY = 512 };
 static const int ES[NE] = {1, 2, 4, 8, 16};
+enum { NT = 4 };
+static const int TS[NT] = {8, 16, 32, 64};
 typedef uint64_t u64;
 
 static int cmp_desc(const void *a, const void *b) {
@@ -101,6 +105,17 @@ int main(int argc, char **argv) {
         vis[(size_t)seeds[s] * W + (s >> 6)] |= 1ull << (s & 63);
         F[seeds[s]] = 1;
     }
+    /* the snapshot's top list (item 14): the 64 atoms of largest (degree, id), descending */
+    int32_t top[64];
+    int ntop = 0;
+    uint8_t *frm = malloc(N), *lrm = malloc(M);
+    {
+        int64_t *key = malloc(sizeof(int64_t) * N);
+        for (int64_t v = 0; v < N; ++v) key[v] = ((io[v + 1] - io[v]) << 32) | v;
+        qsort(key, N, sizeof(int64_t), cmp_desc);
+        for (; ntop < 64 && ntop < N; ++ntop) top[ntop] = (int32_t)(key[ntop] & 0xffffffff);
+        free(key);
+    }
     printf("N %lld M %lld P %lld I %lld S %d\n", (long long)N, (long long)M, (long long)P, (long long)io[N], S);
     for (int d = 0; d < depth; ++d) {
         int64_t nf = 0, alinks = 0, fpins = 0, nnew = 0, cand[2] = {0, 0}, k1[2] = {0, 0}, cover[2] = {0, 0};
@@ -114,6 +129,63 @@ int main(int argc, char **argv) {
             for (int64_t p = off[L]; p < off[L + 1]; ++p) c += F[tg[p]];
             alinks += c > 0;
             fpins += c;
+        }
+        /* hub mask (item 14), per T: C = OR of the level rows of the first T top-list atoms on the frontier; the
+         * fr atoms (frontier atoms with a bit outside C) and their degree sum; the links with an fr atom; per hub
+         * chunk of 4096 entries, one accumulator and the test acc | vis ⊇ C after every 256 entries: the entries
+         * walked until it passes, the entries after it and how many of those have an fr link */
+        for (int ti = 0; ti < NT; ++ti) {
+            u64 C[16] = {0};
+            int listed = 0, pc = 0;
+            for (int k = 0; k < TS[ti] && k < ntop; ++k)
+                if (F[top[k]]) { ++listed; for (int w = 0; w < W; ++w) C[w] |= lvl[(size_t)top[k] * W + w]; }
+            for (int w = 0; w < W; ++w) pc += __builtin_popcountll(C[w]);
+            int64_t nfr = 0, frdeg = 0, frlinks = 0, before = 0, after = 0, after_lr = 0, hub_entries = 0;
+            memset(frm, 0, N);
+#pragma omp parallel for reduction(+ : nfr, frdeg) schedule(static, 4096)
+            for (int64_t v = 0; v < N; ++v) {
+                if (!F[v]) continue;
+                u64 o = 0;
+                for (int w = 0; w < W; ++w) o |= lvl[(size_t)v * W + w] & ~C[w];
+                if (o) { frm[v] = 1; ++nfr; frdeg += io[v + 1] - io[v]; }
+            }
+#pragma omp parallel for reduction(+ : frlinks) schedule(static, 4096)
+            for (int64_t L = 0; L < M; ++L) {
+                int c = 0;
+                for (int64_t p = off[L]; p < off[L + 1]; ++p) c |= frm[tg[p]];
+                lrm[L] = (uint8_t)c;
+                frlinks += c;
+            }
+#pragma omp parallel for schedule(dynamic, 16) reduction(+ : before, after, after_lr, hub_entries)
+            for (int64_t t = 0; t < N; ++t) {
+                const int64_t b = io[t], e = io[t + 1];
+                if (e - b <= HEAVY) continue;
+                const u64 *vt = vis + (size_t)t * W;
+                int full = 1;
+                for (int w = 0; w < W; ++w) full &= vt[w] == FULL[w];
+                if (full) continue;
+                hub_entries += e - b;
+                for (int64_t cb = b; cb < e; cb += 4096) {
+                    const int64_t ce = cb + 4096 < e ? cb + 4096 : e;
+                    u64 acc[16] = {0};
+                    int64_t i = cb;
+                    int pass = 0;
+                    for (; i < ce && !pass;) {
+                        const int64_t se = i + 256 < ce ? i + 256 : ce;
+                        for (; i < se; ++i)
+                            for (int64_t p = off[inc[i]]; p < off[inc[i] + 1]; ++p)
+                                if (F[tg[p]]) for (int w = 0; w < W; ++w) acc[w] |= lvl[(size_t)tg[p] * W + w];
+                        pass = listed > 0;
+                        for (int w = 0; w < W; ++w) pass &= ((acc[w] | vt[w] | ~C[w]) & FULL[w]) == FULL[w];
+                    }
+                    before += i - cb;
+                    for (; i < ce; ++i) { ++after; after_lr += lrm[inc[i]]; }
+                }
+            }
+            printf("  hub mask T=%-2d: listed on the frontier %d |C| %d; fr atoms %lld degree sum %lld; links with an fr atom %lld; "
+                   "hub entries %lld: before the switch %lld, after %lld of which lr-set %lld (%.1f%%)\n", TS[ti], listed, pc,
+                   (long long)nfr, (long long)frdeg, (long long)frlinks, (long long)hub_entries, (long long)before,
+                   (long long)after, (long long)after_lr, after ? 100.0 * after_lr / after : 0.0);
         }
         memset(used, 0, (size_t)M * NE);
         memset(nxt, 0, (size_t)N * W * 8);
