@@ -4807,7 +4807,12 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
     u64* hm_fr = hm_ok ? (u64*)g->alloc(2 * bm_bytes) : nullptr;   // ff: two bits an atom
     u64* hm_lr = hm_ok ? (u64*)g->alloc(la_bytes) : nullptr;
     int hm_levels = 0;
-    const int max_levels_cap = 4096;
+    // level counters: level d counts into block d % ctr_ring (a block is read at most two levels after its level
+    // was issued and cleared up to kZeroLevels levels before it: a traversal has no level limit), then one block
+    // of scratch slots
+    constexpr int ctr_ring = 4096;
+    static_assert(ctr_ring % kZeroLevels == 0, "the counter ring is cleared in whole kZeroLevels runs");
+    const int max_levels_cap = ctr_ring + 1;
     u64* ctr = (u64*)g->alloc(sizeof(u64) * kCtrBlock * max_levels_cap);
     int32_t* d_atoms = (int32_t*)g->alloc(sizeof(int32_t) * seed_atoms.size());
     u64* d_rows = (u64*)g->alloc(sizeof(u64) * seed_rows.size());
@@ -5055,11 +5060,11 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         return true;
     };
 
-    for (int32_t d = 0; d < maxd && d < max_levels_cap - 1 && !stop; ++d) {
+    for (int32_t d = 0; d < maxd && !stop; ++d) {
         if ((d + 1) % kZeroLevels == 0) {   // the next kZeroLevels counter blocks / count rows
             ZeroList zl{};
-            const int64_t b0 = d + 1, b1 = std::min<int64_t>(b0 + kZeroLevels, max_levels_cap - 1);
-            zl.add(ctr + (size_t)b0 * kCtrBlock, sizeof(u64) * kCtrBlock * (size_t)(b1 - b0));
+            const int64_t b0 = d + 1, b1 = b0 + kZeroLevels;
+            zl.add(ctr + (size_t)(b0 % ctr_ring) * kCtrBlock, sizeof(u64) * kCtrBlock * (size_t)kZeroLevels);
             if (bt.pcnt && b0 < kDirectLevels)
                 zl.add(bt.pcnt + (size_t)b0 * 1024, sizeof(u64) * 1024 * (size_t)(std::min<int64_t>(b1, kDirectLevels) - b0));
             zl.launch(s);
@@ -5074,7 +5079,7 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         const bool spec = npend > 0;   // issued before the previous level's counters were read
         u64* lvl_next = (u64*)g->alloc(row_bytes);
         u64* fa_next = (u64*)g->alloc(bm_bytes);   // every word written by hgx_atom_pull
-        u64* c = ctr + (size_t)d * kCtrBlock;
+        u64* c = ctr + (size_t)(d % ctr_ring) * kCtrBlock;
         uint32_t* lv_cpart = nullptr;   // fused counts of this level's new rows (lv_cblk block partials)
         int32_t lv_cblk = 0;
         const bool sparse = spec || (sparse_ok && push_volume < sparse_limit);
@@ -5544,8 +5549,7 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         // guess only costs speed); an empty frontier costs it three near-empty launches, so the
         // counters are read one level late.
         for (;;) {
-            const bool can_spec = pipe_ok && npend == 1 && opush && push_volume < sparse_limit && d + 1 < maxd &&
-                                  d + 1 < max_levels_cap - 1;
+            const bool can_spec = pipe_ok && npend == 1 && opush && push_volume < sparse_limit && d + 1 < maxd;
             if (npend == 0 || can_spec) break;
             Pend& p = pend[(d - npend + 1) & 1];   // the oldest unread level
             --npend;

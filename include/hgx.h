@@ -152,7 +152,10 @@ typedef struct hgx_bfs_stats {
     double  bytes_coop;
     int64_t block_coop;
     /* multi-workgroup launches whose grid barrier timed out (their workgroups were not all resident
-     * within the limit): the bitmaps were cleared and the seeds ran on the rows engine instead */
+     * within the limit): the bitmaps were cleared and the seeds ran on the rows engine instead.  Only
+     * barrier timeouts are counted: a launch that stopped at its level cap or at a capacity
+     * (HGX_OPT_BFS_BLOCK) hands its seeds over in the same way without counting here; those seeds show
+     * in block_rerun. */
     int64_t coop_fallbacks;
     /* levels of the rows engine (summed over batches) whose per-source counts the result readout still
      * has to count with a pass over the level's rows: not counted by the kernels that wrote them
@@ -512,15 +515,28 @@ int  hgx_shard_graph_create(const hgx_shard *s, int32_t device, hgx_graph **out)
  * fixed-grid kernels a level that read every size from device memory; the host polls each level's
  * size one level behind; discoveries ranked by a bitmap over the level's key space);
  * 1 = every seed on the round-1 key-array engine (rocPRIM sort, two host round trips a level; A/B);
- * 2 = every seed on the level-synchronous engine (tests). */
+ * 2 = every seed on the level-synchronous engine (tests).
+ * Level cap of the grid stage: between the two engines of 0, up to 64 handed-over seeds of a generator
+ * with a yield adjacency (hgx_seq_result_grid_stats) first run in one multi-workgroup launch, which
+ * expands the atoms at distances 0 .. 1023 and no further.  A launch in which an atom at distance 1024
+ * still has something to expand -- a traversal whose deepest distance exceeds 1024, or equals 1024 with a
+ * non-empty yield list on an atom at that distance -- hands all its seeds to the level-synchronous
+ * engine, which has no level limit; the results are identical.  A deepest distance of 1023 always stays. */
 #define HGX_OPT_SEQ_ENGINE 13
 /* HGX_OPT_BFS_BLOCK (default 1): hgx_bfs_batch on a whole snapshot first runs every seed in one
  * workgroup (its visited set, frontier and staging in LDS, all its levels in one launch; V_d written
- * into mapped host memory); the seeds whose traversal outgrows the workgroup (more than 1534 atoms,
- * a level wider than 1024 atoms, or a frontier of more than 4M incidence entries) then run on the
+ * into mapped host memory); the seeds whose traversal outgrows the workgroup (more than 1534 atoms
+ * past the seed, a level wider than 1024 atoms, or a frontier of more than 4M incidence entries) then run on the
  * batched rows engine -- up to 64 of them first on the multi-workgroup stage (one persistent launch,
  * a grid barrier per level, per-seed visited bitmaps).  0 = every seed on the rows engine; 2 (tests) =
  * a batch of <= 64 seeds straight to the multi-workgroup stage.  Results are identical either way.
+ * Level cap of the multi-workgroup stage: it expands the atoms at distances 0 .. 1023 and no further.  A
+ * launch in which an atom at distance 1024 still has something to expand (an incident link in the
+ * symmetric mode, a non-empty yield list otherwise) -- a traversal whose deepest distance exceeds 1023 in
+ * the symmetric mode; in an ordered mode one deeper than 1024, or of 1024 with such an atom -- hands all
+ * its seeds to the rows engine (counted in hgx_bfs_stats.block_rerun, not in coop_fallbacks), with
+ * identical results; a max_depth <= 1024 ends a traversal before the cap.  The workgroup stage (one
+ * level per atom at most: 1534) and the rows engine have no level limit of their own.
  * Memory: in an ordered generator mode, or with a link type, both stages and hgx_bfs_sequence's
  * workgroup engine build on first use (kept on the snapshot, shared by its contexts, dropped by
  * hgx_graph_update) the generator's output per atom for that (mode, type, minimum arity, order):
