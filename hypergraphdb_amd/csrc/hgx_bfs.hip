@@ -41,21 +41,6 @@ namespace hgx {
 typedef unsigned long long u64;
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 
-enum Mode { kSym = 0, kAfterFirst = 1, kBeforeFirst = 2, kBeforeLast = 3, kAfterLast = 4 };
-
-// Mirrors pyref.mode_of (validated exhaustively against the DefaultALGenerator restatement).
-static int mode_of(const hgx_algen_opts& o) {
-    bool P = o.return_preceding, S = o.return_succeeding, R = o.reverse_order, RS = o.return_source;
-    if (!R) {
-        if (!P) return kAfterFirst;
-        if (!S && !RS) return kBeforeFirst;
-        return kSym;
-    }
-    if (!P) return kBeforeLast;
-    if (!S && !RS) return kAfterLast;
-    return kSym;
-}
-
 // W words of 64 bits per row; each lane of a G-lane group holds WPL words (16 B loads for W >= 2).
 template <int W> struct Lay {
     static constexpr int WPL = W >= 2 ? 2 : 1;
@@ -198,6 +183,22 @@ enum Ctr {
     cNum = 16
 };
 
+// The kind of a level, as hgx_bfs_stats.level_sparse reports it (include/hgx.h).  Every kind is exact on any
+// frontier: the choice (LevelLoop::plan) only decides the speed.
+enum LevelKind {
+    kLvDense = 0,          // gather every link, pull every atom
+    kLvSparseGather = 1,   // gather the frontier's links, push their lf rows (symmetric mode)
+    kLvPush = 2,           // frontier-driven push
+    kLvDirectPull = 3,     // the atoms not yet visited by every traversal pull from the frontier rows
+    kLvFcPull = 4          // frontier-code pull
+};
+// One expanded level as the host read it: its counters, its kind and the listed atoms its hint step decided.
+struct LevelRec {
+    u64 c[cNum];
+    LevelKind kind;
+    u64 hinted;
+};
+
 __device__ __forceinline__ void wave_add(u64* ctr, u64 v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(ctr, v);
@@ -208,6 +209,18 @@ __device__ __forceinline__ void wave_add(u64* ctr, u64 v) {
 // of shard k lives at base[k * kCtrStride + c]; the host sums the shards.
 constexpr int kCtrShards = 16, kCtrStride = 16, kCtrBlock = kCtrShards * kCtrStride;
 constexpr int kHostSlot = 32;   // u64 words of one level's counters in mapped host memory (cNum + sequence)
+// The bits of HGX_OPT_BFS_FLAGS (include/hgx.h describes them), handed to the kernels with the level's flags.
+constexpr int kGatherEarly = 1 << 0;    // gather early exit
+constexpr int kPullEarly = 1 << 1;      // pull early exit
+constexpr int kSkipFull = 1 << 2;       // skip atoms / links visited by every traversal
+constexpr int kSparseLevels = 1 << 3;   // frontier-driven sparse levels
+constexpr int kSkipFullLate = 1 << 4;   // kSkipFull only once 1/16 of the atoms are visited by every traversal
+constexpr int kSymPush = 1 << 5;        // sparse levels of the symmetric mode push from the frontier atoms
+constexpr int kOneRowDense = 1 << 6;    // keep the one-row-at-a-time dense kernels
+constexpr int kAllRowsOpt = 1 << 7;     // a dense level may write every lf row (kAllRows)
+constexpr int kNfLate = 1 << 8;         // late dense levels pull from the frontier rows directly
+constexpr int kPipePush = 1 << 9;       // ordered-mode push levels are pipelined
+constexpr int kPullHalf = 1 << 11;      // the dense pull keeps half of a lane group's rows in flight (A/B)
 // Internal per-level flag (above the HGX_OPT_BFS_FLAGS bits): dense level with every lf row written.
 constexpr int kAllRows = 1 << 16;
 // Cache-policy A/B bits of HGX_OPT_BFS_FLAGS for the tile-staged dense kernels (gather2 / pull2).
@@ -352,7 +365,7 @@ __global__ void __launch_bounds__(256) hgx_link_gather(int64_t M, const int64_t*
                                                        int flags, const u64* __restrict__ lcand,
                                                        u64* __restrict__ cand) {
     constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G, PW = Lay<W>::PER_WAVE;
-    const bool early = flags & 1, skip_full = flags & 4;
+    const bool early = flags & kGatherEarly, skip_full = flags & kSkipFull;
     typedef Vec<WPL> V;
     const int lane = threadIdx.x & 63, g = lane / G, sub = lane & (G - 1);
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
@@ -587,7 +600,7 @@ __global__ void __launch_bounds__(256) hgx_atom_pull(int64_t A, const int64_t* _
                                                      u64* __restrict__ fa_next, u64* __restrict__ ctr, FullMask fm,
                                                      int flags, const u64* __restrict__ cand) {
     constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G, PW = Lay<W>::PER_WAVE;
-    const bool early = flags & 2, skip_full = flags & 4;
+    const bool early = flags & kPullEarly, skip_full = flags & kSkipFull;
     typedef Vec<WPL> V;
     const int lane = threadIdx.x & 63, g = lane / G, sub = lane & (G - 1);
     const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
@@ -673,7 +686,7 @@ __device__ __forceinline__ void gather2_body(int64_t M, const int64_t* __restric
     constexpr int WPL = Lay<W>::WPL, G = Lay<W>::G, PW = Lay<W>::PER_WAVE;
     static_assert(G >= 4, "gather2 needs G >= 4");
     typedef Vec<WPL> V;
-    const bool early = flags & 1, skip_full = flags & 4, all_rows = flags & kAllRows;
+    const bool early = flags & kGatherEarly, skip_full = flags & kSkipFull, all_rows = flags & kAllRows;
     const bool nt_idx = flags & kNtIdx, nt_lf = flags & kNtLf;
     const int lane = threadIdx.x & 63, g = lane / G, sub = lane & (G - 1), base = lane & ~(G - 1);
     const u64 gmask = (1ull << G) - 1ull;
@@ -826,7 +839,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KR < L
     __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
     __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
     if (cpart) fuse_zero<W>(cplanes, &cdone);
-    const bool early = flags & 2, skip_full = flags & 4, all_rows = flags & kAllRows;
+    const bool early = flags & kPullEarly, skip_full = flags & kSkipFull, all_rows = flags & kAllRows;
     const bool nt_idx = flags & kNtIdx, nt_out = flags & kNtOut;
     const int lane = threadIdx.x & 63, g = lane / G, sub = lane & (G - 1), base = lane & ~(G - 1);
     const u64 gmask = (1ull << G) - 1ull;
@@ -1064,7 +1077,7 @@ __global__ void __launch_bounds__(256) hgx_atom_pull_heavy(const HeavyChunk* __r
     typedef Vec<WPL> V;
     __shared__ u64 red[NG * W];
     const HeavyChunk c = chunks[blockIdx.x];
-    if ((flags & 4) && bit(full, c.atom)) return;   // block-uniform
+    if ((flags & kSkipFull) && bit(full, c.atom)) return;   // block-uniform
     if (cand && !bit(cand, c.atom)) return;
     const int sub = threadIdx.x & (G - 1);
     const int gi = threadIdx.x / G;
@@ -1078,15 +1091,15 @@ __global__ void __launch_bounds__(256) hgx_atom_pull_heavy(const HeavyChunk* __r
     bool have_old = false;
     bool done = false;
     if constexpr (G >= 4 && MODE == kSym) {
-        if (b < e && (flags & kHeavyMlp2) && (flags & kAllRows) && !(flags & 4)) {   // block-uniform
+        if (b < e && (flags & kHeavyMlp2) && (flags & kAllRows) && !(flags & kSkipFull)) {   // block-uniform
             pull_range_mlp<W, 2>(b, e, inc_row, la, lf, vis + (int64_t)c.atom * W, bit(ever, c.atom), FULL, sub, acc,
-                                 old, have_old, n_inc, n_vis, (flags & 2) != 0, true);
+                                 old, have_old, n_inc, n_vis, (flags & kPullEarly) != 0, true);
             done = true;
         }
     }
     if (b < e && !done)
         pull_range<W, MODE>(c.atom, b, e, inc_row, la, lf, tgt_off, tgt_idx, fa, lvl, vis + (int64_t)c.atom * W,
-                            bit(ever, c.atom), FULL, sub, acc, old, have_old, n_inc, n_vis, (flags & 2) != 0);
+                            bit(ever, c.atom), FULL, sub, acc, old, have_old, n_inc, n_vis, (flags & kPullEarly) != 0);
     V::st(red + gi * W + sub * WPL, acc);
     __syncthreads();
     for (int j = threadIdx.x; j < W; j += 256) {
@@ -1304,11 +1317,11 @@ __global__ void __launch_bounds__(256) hgx_atom_pull_hub(const HeavyChunk* __res
     typedef Vec<WPL> V;
     __shared__ __attribute__((aligned(16))) u64 red[NG * W];   // step off: a row per group; on: [2][4][W] wave rows
     const HeavyChunk c = chunks[blockIdx.x];
-    if ((flags & 4) && bit(full, c.atom)) return;   // block-uniform
+    if ((flags & kSkipFull) && bit(full, c.atom)) return;   // block-uniform
     const int sub = threadIdx.x & (G - 1);
     const int gi = threadIdx.x / G;
     const typename V::T FULL = full_part<W>(fm, sub);
-    const bool early = (flags & 2) != 0;
+    const bool early = (flags & kPullEarly) != 0;
     u64 n_inc = 0, n_vis = 0, n_filt = 0, n_skip = 0;
     typename V::T acc = V::zero(), old = V::zero();
     if (!hub_mask_on(hm, mode, S, deg_limit)) {   // block-uniform
@@ -2470,7 +2483,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
     __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
     if (cpart) fuse_zero<W>(cplanes, &cdone);
-    const bool early = flags & 2;
+    const bool early = flags & kPullEarly;
     const int lane = threadIdx.x & 63, sub = lane & (G - 1);
     const int64_t grp = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) / G;
     const int64_t ngrp = ((int64_t)gridDim.x * blockDim.x) / G;
@@ -2558,7 +2571,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))
     __shared__ u64 cplanes[kFusePlanes * W];   // fused level counts (cpart != null; block-uniform)
     __shared__ unsigned int cdone;             //   waves of the block that have added all their rows
     if (cpart) fuse_zero<W>(cplanes, &cdone);
-    const bool early = flags & 2;
+    const bool early = flags & kPullEarly;
     const int lane = threadIdx.x & 63, sub = lane & (G - 1), base = lane & ~(G - 1);
     const int my_a = sub / E, my_e = sub % E;
     const u64 gmask = (1ull << G) - 1ull;
@@ -2758,7 +2771,7 @@ __global__ void __launch_bounds__(256) hgx_nf_pull_heavy(const HeavyChunk* __res
         const typename V::T old = bit(ever, c.atom) ? V::ld(vis + (int64_t)c.atom * W + sub * WPL) : V::zero();
         typename V::T acc = V::zero();
         if (b < e)   // group-uniform
-            nf_range<W>(b, e, inc_row, inc_type, want_type, tgt_off, tgt_idx, fa, lvl, FULL, old, acc, (flags & 2) != 0,
+            nf_range<W>(b, e, inc_row, inc_type, want_type, tgt_off, tgt_idx, fa, lvl, FULL, old, acc, (flags & kPullEarly) != 0,
                         n_ent, n_pins, n_rows);
         V::st(red + gi * W + sub * WPL, acc);
         __syncthreads();
@@ -3061,7 +3074,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
     __shared__ int32_t spre[T + 1];
     __shared__ int32_t wsum[4];
     __shared__ u64 snew[NW], sfull[NW];
-    const bool skip_full = flags & 4;
+    const bool skip_full = flags & kSkipFull;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int sub = tid & (G - 1), gi = tid / G;
     const typename V::T FULL = full_part<W>(fm, sub);
@@ -3203,7 +3216,7 @@ __global__ void __launch_bounds__(256) hgx_fc_pull_heavy(const HeavyChunk* __res
     __shared__ u64 hubtab[kFcHubs];
     __shared__ int covered;
     const HeavyChunk c = chunks[blockIdx.x];
-    if ((flags & 4) && bit(full, c.atom)) return;   // block-uniform
+    if ((flags & kSkipFull) && bit(full, c.atom)) return;   // block-uniform
     const int tid = threadIdx.x;
     if (tid < W) acc[tid] = 0ull;
     if (tid < kFcDW) dmask[tid] = 0ull;
@@ -4267,27 +4280,30 @@ constexpr double kFcFrontBytes = 64.0 * (1 << 20);
 // snapshots (config 4: 32 GB) keep gather + pull rather than hold that much next to the level rows.
 constexpr size_t kFcRecBudget = (size_t)16 << 30;
 
-// The snapshot's per-entry target records (hgx_fc_rec), built on first use on the root snapshot and
-// shared by its contexts; nullptr when over budget, when a quarter of the free device memory cannot
-// hold them, or when some link has more than 8 targets.  Caller holds g->mu.
+// The heavy atoms of `of` and their degrees, on the host (scratch from g's pool; waits for the stream).
+void heavy_degrees(hgx_graph* g, const hgx_graph* of, hipStream_t s, std::vector<int32_t>& ids,
+                   std::vector<int64_t>& deg) {
+    const int64_t nh = of->n_heavy;
+    ids.resize((size_t)nh);
+    deg.resize((size_t)nh);
+    PoolScratch sc{g, {}};
+    int64_t* dd = (int64_t*)sc.take(sizeof(int64_t) * (size_t)nh);
+    hgx_fc_deg<<<grid_for(nh, 256, 4096), 256, 0, s>>>(nh, of->heavy_atom, of->inc_off, dd);
+    HGX_CHECK_LAUNCH();
+    HGX_HIP(hipMemcpyAsync(ids.data(), of->heavy_atom, sizeof(int32_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
+    HGX_HIP(hipMemcpyAsync(deg.data(), dd, sizeof(int64_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
+    HGX_HIP(hipStreamSynchronize(s));
+}
+
 // The snapshot's top list (HGX_OPT_HUB_MASK): its kHubTop atoms of largest (degree, id), descending, built in
 // the stream on first use like nbr_hint.  Every hub outranks every light atom, so the hubs' degrees decide
 // when there are kHubTop hubs; a smaller snapshot sorts all its degrees.  Caller holds g->mu.
-void hub_top_list(hgx_graph* g, hipStream_t s) {
+void ensure_top_list(hgx_graph* g, hipStream_t s) {
     if (g->top_list) return;
     std::vector<int32_t> ids;
     std::vector<int64_t> deg;
     if (g->n_heavy >= kHubTop) {
-        const int64_t nh = g->n_heavy;
-        ids.resize((size_t)nh);
-        deg.resize((size_t)nh);
-        int64_t* dd = (int64_t*)g->alloc(sizeof(int64_t) * (size_t)nh);
-        hgx_fc_deg<<<grid_for(nh, 256, 4096), 256, 0, s>>>(nh, g->heavy_atom, g->inc_off, dd);
-        HGX_CHECK_LAUNCH();
-        HGX_HIP(hipMemcpyAsync(ids.data(), g->heavy_atom, sizeof(int32_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
-        HGX_HIP(hipMemcpyAsync(deg.data(), dd, sizeof(int64_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
-        HGX_HIP(hipStreamSynchronize(s));
-        g->release(dd, sizeof(int64_t) * (size_t)nh);
+        heavy_degrees(g, g, s, ids, deg);
     } else {
         std::vector<int64_t> off((size_t)g->A + 1);
         HGX_HIP(hipMemcpyAsync(off.data(), g->inc_off, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost, s));
@@ -4313,7 +4329,10 @@ void hub_top_list(hgx_graph* g, hipStream_t s) {
     g->top_n = (int32_t)keep;
 }
 
-const int4* fc_records(hgx_graph* g, hipStream_t s) {
+// The snapshot's per-entry target records (hgx_fc_rec), built on first use on the root snapshot and
+// shared by its contexts; nullptr when over budget, when a quarter of the free device memory cannot
+// hold them, or when some link has more than 8 targets.  Caller holds g->mu.
+const int4* ensure_fc_records(hgx_graph* g, hipStream_t s) {
     hgx_graph* root = g->base ? g->base : g;
     std::lock_guard<std::mutex> lk(root->ylist_mu);
     if (root->fc_rec_state == 0) {
@@ -4327,15 +4346,9 @@ const int4* fc_records(hgx_graph* g, hipStream_t s) {
             std::vector<int32_t> hubs;
             if (root->n_heavy > 0) {
                 const int64_t nh = root->n_heavy;
-                std::vector<int32_t> ha((size_t)nh);
-                std::vector<int64_t> hd((size_t)nh);
-                int64_t* dd = (int64_t*)g->alloc(sizeof(int64_t) * (size_t)nh);
-                hgx_fc_deg<<<grid_for(nh, 256, 4096), 256, 0, s>>>(nh, root->heavy_atom, root->inc_off, dd);
-                HGX_CHECK_LAUNCH();
-                HGX_HIP(hipMemcpyAsync(ha.data(), root->heavy_atom, sizeof(int32_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
-                HGX_HIP(hipMemcpyAsync(hd.data(), dd, sizeof(int64_t) * (size_t)nh, hipMemcpyDeviceToHost, s));
-                HGX_HIP(hipStreamSynchronize(s));
-                g->release(dd, sizeof(int64_t) * (size_t)nh);
+                std::vector<int32_t> ha;
+                std::vector<int64_t> hd;
+                heavy_degrees(g, root, s, ha, hd);
                 std::vector<int64_t> ord((size_t)nh);
                 for (int64_t k = 0; k < nh; ++k) ord[(size_t)k] = k;
                 const size_t keep = std::min<size_t>((size_t)nh, (size_t)kFcHubs);
@@ -4349,7 +4362,8 @@ const int4* fc_records(hgx_graph* g, hipStream_t s) {
                 HGX_HIP(hipMalloc(&dh, sizeof(int32_t) * hubs.size()));
                 HGX_HIP(hipMemcpyAsync(dh, hubs.data(), sizeof(int32_t) * hubs.size(), hipMemcpyHostToDevice, s));
             }
-            unsigned int* dov = (unsigned int*)g->alloc(16);
+            PoolScratch sc{g, {}};
+            unsigned int* dov = (unsigned int*)sc.take(16);
             HGX_HIP(hipMemsetAsync(dov, 0, sizeof(unsigned int), s));
             hgx_fc_rec<<<grid_for(root->I, 256, 16384), 256, 0, s>>>(root->A, root->I, root->inc_off, root->inc_row,
                                                                       root->tgt_off, root->tgt_idx, dh,
@@ -4358,7 +4372,6 @@ const int4* fc_records(hgx_graph* g, hipStream_t s) {
             unsigned int over = 1;
             HGX_HIP(hipMemcpyAsync(&over, dov, sizeof(unsigned int), hipMemcpyDeviceToHost, s));
             HGX_HIP(hipStreamSynchronize(s));
-            g->release(dov, 16);
             if (over) {
                 (void)hipFree(rec);
                 if (dh) (void)hipFree(dh);
@@ -4392,13 +4405,15 @@ __global__ void __launch_bounds__(256) hgx_push_heavy_find(int64_t A, const int6
 
 // The frontier push's chunk table (once per snapshot): kPushChunk-entry chunks of every atom with
 // more than kPushLight incidences, in atom order.
-void build_push_chunks(hgx_graph* g) {
+void ensure_push_chunks(hgx_graph* g) {
+    if (g->n_pchunks >= 0) return;
     hipStream_t s = g->stream;
     const int64_t A = g->A;
     // at most I / (kPushLight + 1) atoms have more than kPushLight incidences
     const int64_t nmax = std::min<int64_t>(g->I / (kPushLight + 1) + 1, std::max<int64_t>(A, 1));
-    int64_t* dout = (int64_t*)g->alloc(sizeof(int64_t) * 3 * (size_t)nmax);
-    unsigned int* dn = (unsigned int*)g->alloc(16);
+    PoolScratch sc{g, {}};
+    int64_t* dout = (int64_t*)sc.take(sizeof(int64_t) * 3 * (size_t)nmax);
+    unsigned int* dn = (unsigned int*)sc.take(16);
     HGX_HIP(hipMemsetAsync(dn, 0, 4, s));
     hgx_push_heavy_find<<<grid_for(A, 256, 4096), 256, 0, s>>>(A, g->inc_off, kPushLight, dout, dn);
     HGX_CHECK_LAUNCH();
@@ -4408,8 +4423,6 @@ void build_push_chunks(hgx_graph* g) {
     std::vector<int64_t> h(3 * (size_t)nh);
     if (nh) HGX_HIP(hipMemcpyAsync(h.data(), dout, sizeof(int64_t) * 3 * nh, hipMemcpyDeviceToHost, s));
     HGX_HIP(hipStreamSynchronize(s));
-    g->release(dout, sizeof(int64_t) * 3 * (size_t)nmax);
-    g->release(dn, 16);
     std::vector<size_t> ord(nh);
     for (size_t i = 0; i < nh; ++i) ord[i] = i;
     std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return h[3 * x] < h[3 * y]; });
@@ -4424,6 +4437,50 @@ void build_push_chunks(hgx_graph* g) {
         HGX_HIP(hipMemcpyAsync(g->pchunks, ch.data(), sizeof(HeavyChunk) * ch.size(), hipMemcpyHostToDevice, s));
     HGX_HIP(hipStreamSynchronize(s));
     g->n_pchunks = (int64_t)ch.size();
+}
+
+// The other snapshot tables, each built in the stream on first use (caller holds g->mu): the has-incidence bitmap,
+void ensure_hasinc(hgx_graph* g, hipStream_t s) {
+    if (g->hasinc) return;
+    const int64_t A = g->A;
+    HGX_HIP(hipMalloc(&g->hasinc, sizeof(u64) * (size_t)(ceil_div(A, 64) + 1)));
+    hgx_hasinc<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(A, g->inc_off, (u64*)g->hasinc);
+    HGX_CHECK_LAUNCH();
+}
+
+// the direct pull's hint entries (the light atoms' by hgx_nbr_hint, the heavy atoms' from their chunks),
+void ensure_nbr_hint(hgx_graph* g, hipStream_t s) {
+    if (g->nbr_hint) return;
+    const int64_t A = g->A;
+    HGX_HIP(hipMalloc(&g->nbr_hint, sizeof(int32_t) * (size_t)std::max<int64_t>(A, 1)));
+    hgx_nbr_hint<<<grid_for(A * 8, 256, 8192), 256, 0, s>>>(A, g->inc_off, g->inc_row, g->tgt_off, g->tgt_idx,
+                                                           g->nbr_hint);
+    HGX_CHECK_LAUNCH();
+    if (g->n_chunks > 0) {
+        PoolScratch sc{g, {}};   // (stream-ordered reuse)
+        const size_t hk_bytes = sizeof(u64) * (size_t)g->n_heavy;
+        u64* hkey = (u64*)sc.take(hk_bytes);
+        HGX_HIP(hipMemsetAsync(hkey, 0, hk_bytes, s));
+        hgx_nbr_hint_heavy<<<(int)std::min<int64_t>(g->n_chunks, 8192), 256, 0, s>>>(
+            g->chunks, g->n_chunks, g->inc_off, g->inc_row, g->tgt_off, g->tgt_idx, hkey);
+        HGX_CHECK_LAUNCH();
+        hgx_nbr_hint_heavy_out<<<grid_for(g->n_heavy, 256, 1024), 256, 0, s>>>(g->n_heavy, g->heavy_atom, hkey,
+                                                                               g->nbr_hint);
+        HGX_CHECK_LAUNCH();
+    }
+}
+
+// and the frontier push's all-zero accumulator of row_bytes at least (kept zero by the push finalise: zacc_clean).
+void ensure_zacc(hgx_graph* g, size_t row_bytes, hipStream_t s) {
+    if (g->zacc_clean && g->zacc_bytes >= row_bytes) return;
+    if (g->zacc_bytes < row_bytes) {
+        if (g->zacc) HGX_HIP(hipFree(g->zacc));
+        g->zacc = nullptr;
+        g->zacc_bytes = 0;
+        HGX_HIP(hipMalloc(&g->zacc, row_bytes));
+        g->zacc_bytes = row_bytes;
+    }
+    HGX_HIP(hipMemsetAsync(g->zacc, 0, g->zacc_bytes, s));
 }
 
 FullMask full_mask(int S, int W) {
@@ -4469,6 +4526,7 @@ struct Exchange {
     hgx_graph* g;
     Transport* tr;
     int W;
+    PoolScratch pool{g, {}};            // the device buffers below
     int64_t cap_recs = 0;               // send / receive area capacity (records)
     u64* send_h = nullptr;              // header streams (2 words per record)
     u64* recv_h = nullptr;
@@ -4495,13 +4553,13 @@ struct Exchange {
         }
         cap_recs = std::max<int64_t>(std::max(rseg[NP], bseg[NP]), 1);
         if (cap_recs >= ((int64_t)1 << 32)) fail(HGX_E_INVALID, "partitioned BFS: exchange segment above 2^32 records");
-        send_h = (u64*)g->alloc(sizeof(u64) * 2 * (size_t)cap_recs);
-        recv_h = (u64*)g->alloc(sizeof(u64) * 2 * (size_t)cap_recs);
-        send_p = (u64*)g->alloc(sizeof(u64) * W * (size_t)cap_recs);
-        recv_p = (u64*)g->alloc(sizeof(u64) * W * (size_t)cap_recs);
-        dctr = (u64*)g->alloc(sizeof(u64) * (NP * kCurStride + kStatShards * kStatStride));
-        dvec = (int64_t*)g->alloc(sizeof(int64_t) * (2 * NP + 2));
-        seg = (int64_t*)g->alloc(sizeof(int64_t) * 4 * NP);
+        send_h = (u64*)pool.take(sizeof(u64) * 2 * (size_t)cap_recs);
+        recv_h = (u64*)pool.take(sizeof(u64) * 2 * (size_t)cap_recs);
+        send_p = (u64*)pool.take(sizeof(u64) * W * (size_t)cap_recs);
+        recv_p = (u64*)pool.take(sizeof(u64) * W * (size_t)cap_recs);
+        dctr = (u64*)pool.take(sizeof(u64) * (NP * kCurStride + kStatShards * kStatStride));
+        dvec = (int64_t*)pool.take(sizeof(int64_t) * (2 * NP + 2));
+        seg = (int64_t*)pool.take(sizeof(int64_t) * 4 * NP);
         std::vector<int64_t> hs(4 * (size_t)NP);
         for (int q = 0; q < NP; ++q) {
             hs[q] = rseg[q];
@@ -4523,14 +4581,6 @@ struct Exchange {
     ~Exchange() {
         if (hpin) (void)hipHostFree(hpin);
         if (gpin) (void)hipHostFree(gpin);
-        const int NP = g->shard->n_parts;
-        g->release(dvec, sizeof(int64_t) * (2 * NP + 2));
-        g->release(send_h, sizeof(u64) * 2 * (size_t)cap_recs);
-        g->release(recv_h, sizeof(u64) * 2 * (size_t)cap_recs);
-        g->release(send_p, sizeof(u64) * W * (size_t)cap_recs);
-        g->release(recv_p, sizeof(u64) * W * (size_t)cap_recs);
-        g->release(dctr, sizeof(u64) * (NP * kCurStride + kStatShards * kStatStride));
-        g->release(seg, sizeof(int64_t) * 4 * NP);
     }
     // collective step: the part's device work is bracketed by compute_begin / compute_end
     template <class F>
@@ -4767,251 +4817,690 @@ struct Exchange {
     }
 };
 
-template <int W, int MODE>
-void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_depth, int32_t want_type,
-                const std::vector<int32_t>& seed_atoms, const std::vector<u64>& seed_rows, Timer& tm,
-                std::vector<std::vector<u64>>& level_ctr, Transport* tr) {
-    hipStream_t s = g->stream;
-    const int64_t A = g->A, M = g->M;
-    const size_t row_bytes = sizeof(u64) * (size_t)A * W;
-    const size_t bm_bytes = res->bm_bytes();
-    const size_t la_bytes = sizeof(u64) * (size_t)(M / 64 + 2);
-    const FullMask fm = full_mask(bt.S, W);
-    const u64* own_bm = g->shard ? (const u64*)g->shard->own_bm : nullptr;   // partition part: owned atoms
-    // a partition part's device work runs between compute_begin / compute_end (the exchange releases
-    // it around each collective); the guard releases it on an error path too
-    struct Gate {
-        Transport* tr;
-        hipStream_t s;
-        explicit Gate(Transport* t, hipStream_t st) : tr(t), s(st) {
-            if (tr) tr->compute_begin(s);
-        }
-        ~Gate() {
-            if (tr) tr->compute_release(s);
-        }
-    } gate(tr, s);
+// What LevelLoop::plan decides for a level.
+struct LevelPlan {
+    LevelKind kind;
+    int lflags;          // the level's flags for the kernels
+    const int4* fcrec;   // kLvFcPull: the snapshot's records
+    bool nf_late;        // kLvDirectPull: chosen by the late-level rule (the cover test steps by one entry)
+};
 
-    u64* vis = (u64*)g->alloc(row_bytes);
-    u64* lf = (MODE == kSym) ? (u64*)g->alloc(sizeof(u64) * (size_t)std::max<int64_t>(M, 1) * W) : nullptr;
-    u64* hubacc = (u64*)g->alloc(sizeof(u64) * (size_t)std::max<int64_t>(g->n_heavy, 1) * W);
-    u64* ever = (u64*)g->alloc(bm_bytes);
-    u64* full = (u64*)g->alloc(bm_bytes);
-    u64* la = (u64*)g->alloc(la_bytes);
-    // hub mask (HGX_OPT_HUB_MASK): the two-bit map ff, the links' lr bits, C's row and two rule slots (alternating
-    // over the levels that run the step; both zero after the prologue, then each level clears the other's)
-    bool hm_ok = false;
-    if constexpr (MODE == kSym && Lay<W>::G >= 4)
-        hm_ok = g->hub_mask != 0 && !tr && !g->shard && g->n_chunks > 0;
-    const size_t hm_bytes = sizeof(u64) * (2 * kHmSlot + 16);
-    u64* hm = hm_ok ? (u64*)g->alloc(hm_bytes) : nullptr;   // [2][kHmSlot] slots, then C's row
-    u64* hm_fr = hm_ok ? (u64*)g->alloc(2 * bm_bytes) : nullptr;   // ff: two bits an atom
-    u64* hm_lr = hm_ok ? (u64*)g->alloc(la_bytes) : nullptr;
-    int hm_levels = 0;
+// One batch of the rows engine: the level loop of hgx_bfs_batch / hgx_pbfs_batch with one routine per level
+// kind.  The object owns the batch's pool buffers: pool holds those of the whole batch, tmp those of the level
+// being issued, a Pend the rows of its level until read_level hands them to bt (whose owner is the guard of
+// bfs_batch_impl); an error at any point gives them all back (stream-ordered, like every pool release).
+template <int W, int MODE>
+struct LevelLoop {
+    // A level in flight: issued, its counters not yet read.
+    struct Pend {
+        int32_t d = 0;
+        u64 *lvl_next = nullptr, *fa_next = nullptr;   // the rows it writes
+        u64* c = nullptr;                              // its counter block on the device
+        LevelKind kind = kLvDense;
+        int allrows = 0;
+        u64 new_global = 0, part_push = 0;
+        u64* h = nullptr;
+        hipEvent_t ev = nullptr;
+        bool flag = false;    // counters in slot[0..cNum) once slot[cNum] == seq (mapped host memory)
+        u64 seq = 0, *slot = nullptr;
+        uint32_t* cpart = nullptr;   // fused counts of the level's new rows: cblk block partials
+        int32_t cblk = 0;
+        bool sampled = false;   // hgx_level_sample ran: cDirRows / cScanned carry its sample
+    };
     // level counters: level d counts into block d % ctr_ring (a block is read at most two levels after its level
     // was issued and cleared up to kZeroLevels levels before it: a traversal has no level limit), then one block
     // of scratch slots
-    constexpr int ctr_ring = 4096;
+    static constexpr int ctr_ring = 4096, max_levels_cap = ctr_ring + 1, block = 256;
     static_assert(ctr_ring % kZeroLevels == 0, "the counter ring is cleared in whole kZeroLevels runs");
-    const int max_levels_cap = ctr_ring + 1;
-    u64* ctr = (u64*)g->alloc(sizeof(u64) * kCtrBlock * max_levels_cap);
-    int32_t* d_atoms = (int32_t*)g->alloc(sizeof(int32_t) * seed_atoms.size());
-    u64* d_rows = (u64*)g->alloc(sizeof(u64) * seed_rows.size());
-    // one pinned region: two levels' counters in flight, then the seed atoms and rows going up (a copy
-    // from pageable memory is staged by the runtime and holds the host)
-    const size_t o_atoms = sizeof(u64) * kCtrBlock * 2;
-    const size_t o_rows = (o_atoms + sizeof(int32_t) * seed_atoms.size() + 15) & ~(size_t)15;
-    char* hp = (char*)g->pinned_buf(o_rows + sizeof(u64) * seed_rows.size());
-    u64* h_sh = (u64*)hp;
-    u64 h_new[cNum];
-    std::memcpy(hp + o_atoms, seed_atoms.data(), sizeof(int32_t) * seed_atoms.size());
-    std::memcpy(hp + o_rows, seed_rows.data(), sizeof(u64) * seed_rows.size());
+    static constexpr size_t hm_bytes = sizeof(u64) * (2 * kHmSlot + 16);
 
-    // the prologue's buffers cleared by one launch; level counter blocks (and push-level count rows)
-    // are cleared kZeroLevels at a time as the traversal reaches them
-    bt.lvl.push_back((u64*)g->alloc(row_bytes));
-    bt.fa.push_back((u64*)g->alloc(bm_bytes));
-    const bool sparse_ok = (g->bfs_flags & 8) != 0;
-    u64* lcand = sparse_ok ? (u64*)g->alloc(la_bytes) : nullptr;
-    u64* cand = sparse_ok ? (u64*)g->alloc(bm_bytes) : nullptr;
-    const size_t flist_bytes = sizeof(int32_t) * (size_t)std::max<int64_t>(A, 1);
-    int32_t* flist = sparse_ok ? (int32_t*)g->alloc(flist_bytes) : nullptr;   // frontier list (push levels)
-    int32_t* clist = sparse_ok ? (int32_t*)g->alloc(flist_bytes) : nullptr;   // push candidates
-    ZeroList z{};
-    if (cand) z.add(cand, bm_bytes);   // the first push level's candidate words (no memset of their own)
-    z.add(ever, bm_bytes);
-    z.add(full, bm_bytes);
-    z.add(bt.fa[0], bm_bytes);
-    z.add(hubacc, sizeof(u64) * (size_t)std::max<int64_t>(g->n_heavy, 1) * W);
-    if (hm) z.add(hm, hm_bytes);
-    z.add(ctr, sizeof(u64) * kCtrBlock * kZeroLevels);
-    z.add(ctr + (size_t)(max_levels_cap - 1) * kCtrBlock, sizeof(u64) * kCtrBlock);   // scratch slots
-    if (!tr) {   // per-source counts of push levels, accumulated by their finalise (readout without a pass)
-        bt.pcnt = (u64*)g->alloc(sizeof(u64) * 1024 * kDirectLevels);
-        z.add(bt.pcnt, sizeof(u64) * 1024 * kZeroLevels);
-        bt.direct.assign(kDirectLevels, 0);
+    hgx_graph* const g;
+    hgx_bfs_result* const res;
+    BfsBatch& bt;
+    Timer& tm;
+    std::vector<LevelRec>& level_ctr;
+    Transport* const tr;
+    const int32_t want_type, maxd;
+    const hipStream_t s = g->stream;
+    const int64_t A = g->A, M = g->M, I_total = g->I;
+    const size_t row_bytes = sizeof(u64) * (size_t)A * W, bm_bytes = res->bm_bytes(),
+                 la_bytes = sizeof(u64) * (size_t)(M / 64 + 2),
+                 flist_bytes = sizeof(int32_t) * (size_t)std::max<int64_t>(A, 1);
+    const FullMask fm = full_mask(bt.S, W);
+    const u64* const own_bm = g->shard ? (const u64*)g->shard->own_bm : nullptr;   // partition part: owned atoms
+    ComputeGate gate{tr, s};   // (the exchange releases it around each collective)
+    std::unique_ptr<Exchange> ex;   // one part: no ghosts, nothing to exchange
+    PoolScratch pool{g, {}}, tmp{g, {}};
+    u64 *vis, *lf, *hubacc, *ever, *full, *la, *ctr, *lcand = nullptr, *cand = nullptr;
+    int32_t *flist = nullptr, *clist = nullptr;   // frontier list (push levels), push candidates
+    // hub mask (HGX_OPT_HUB_MASK): the two-bit map ff, the links' lr bits, C's row and two rule slots (alternating
+    // over the levels that run the step; both zero after the prologue, then each level clears the other's)
+    bool hm_ok = false;
+    u64 *hm = nullptr, *hm_fr = nullptr, *hm_lr = nullptr;   // hm: [2][kHmSlot] slots, then C's row; ff: two bits an atom
+    int hm_levels = 0;
+    // push levels: fl = this level's frontier list, cl = its candidates; the finalise turns cl into the
+    // next level's frontier list (chained), so consecutive push levels swap the two
+    int32_t *fl, *cl;
+    u64 *n_fl, *n_cl, *ticket;   // scratch slots; ticket: the finalise's last-block ticket (re-zeroed by that block)
+    // cand was cleared by the prologue launch, and so were the scratch slots n_fl / n_cl (until a level
+    // uses them): the first push level issues no memset (each costs a host API call, ~20 us between
+    // the prologue's device operations on config 5); scratch_zero: they still are, for the level being issued
+    bool chained = false, cand_clean, scratch_clean = true, scratch_zero = true;
+    const bool sparse_ok = (g->bfs_flags & kSparseLevels) != 0;
+    bool eager, fuse_ok, nf_eligible, pipe_ok;
+    const bool trace = trace_env("HGX_BFS_TRACE");   // per-level counters to stderr
+    int64_t full_deg_total = 0;   // sum of |inc(v)| over the atoms visited by every traversal
+    u64 push_volume = 0, push_volume_nf = 0;   // frontier incidence volume (all / not yet full atoms)
+    u64 front_atoms, sparse_limit;             // atoms of the current level's frontier; the push / dense threshold
+    // Full-visited skipping costs two bitmap probes per pin; it pays once a sizeable share of the
+    // atoms is visited by every traversal (seeds that are full count from the start).
+    u64 full_total = 0;
+    const int nf_opt = g->nf_pull;   // the direct-pull rule (HGX_OPT_NF_PULL = 1)
+    int nf_stride = 1;
+    double samp_rows = 0, samp_bits = 0, samp_nf = 0;   // the previous level's sample (zero: the rule does not select)
+    const int gather_grid = grid_for(ceil_div(M, 64) * 64, block, 256 * 16),
+              pull_grid = grid_for(ceil_div(A, 64) * 64, block, 256 * 16),
+              hub_grid = grid_for(std::max<int64_t>(g->n_heavy, 1) * Lay<W>::G, block, 256 * 16);
+    Pend pend[2];   // the levels in flight
+    int npend = 0;
+    bool stop = false;
+    u64 *cur_lvl, *cur_fa;
+
+    static size_t cpart_size(int32_t blocks) { return sizeof(uint32_t) * (size_t)blocks * W * 64; }
+    // Fused level counts (HGX_OPT_COUNT_FUSED, whole-graph batches as for pcnt): the symmetric-mode kernels of rows of
+    // >= 8 words (more than 256 sources) that store a level's new rows (hgx_atom_pull2 + hgx_hub_finalize, hgx_nf_pull)
+    // count them into block partials; every other level kind is counted at readout.  The LDS planes hold < 2^kFusePlanes
+    // rows per workgroup: a workgroup of the pull sees at most ceil(tiles / waves) * 256 rows, one of the hub finalise
+    // or the non-full pull at most ceil(atoms / groups) * (256 / G) -- about A / 4096 + 256 at the full grids, < 2^20
+    // for any int32 atom count; fuse_rows_ok checks the actual grids.
+    static bool fuse_rows_ok(int64_t items, int grid, int per_block) {
+        return ceil_div(items, (int64_t)grid * per_block) * per_block < ((int64_t)1 << kFusePlanes);
     }
-    z.launch(s);
-    HGX_HIP(hipMemcpyAsync(d_atoms, hp + o_atoms, sizeof(int32_t) * seed_atoms.size(), hipMemcpyHostToDevice, s));
-    HGX_HIP(hipMemcpyAsync(d_rows, hp + o_rows, sizeof(u64) * seed_rows.size(), hipMemcpyHostToDevice, s));
-    {
-        int n = (int)seed_atoms.size();
-        hgx_seed<W><<<grid_for(n, 256, 1 << 20), 256, 0, s>>>(n, d_atoms, d_rows, bt.lvl[0], vis, bt.fa[0], ever,
-                                                              full, fm);
+    u64* scratch_slots() const { return ctr + (size_t)(max_levels_cap - 1) * kCtrBlock; }
+    void drop_rows(Pend& p) {   // a level that found nothing, or an error: the rows it still owns go back to the pool
+        if (p.lvl_next) g->release(p.lvl_next, row_bytes);
+        if (p.fa_next) g->release(p.fa_next, bm_bytes);
+        if (p.cpart) g->release(p.cpart, cpart_size(p.cblk));
+        p.lvl_next = p.fa_next = nullptr;
+        p.cpart = nullptr;
+    }
+    ~LevelLoop() {
+        for (Pend& p : pend) drop_rows(p);
+    }
+
+    // Prologue: the batch's buffers, the one clearing launch, the seeds, the seed-volume wait.
+    LevelLoop(hgx_graph* g_, hgx_bfs_result* res_, BfsBatch& bt_, int32_t max_depth, int32_t want_type_,
+              const std::vector<int32_t>& seed_atoms, const std::vector<u64>& seed_rows, Timer& tm_,
+              std::vector<LevelRec>& level_ctr_, Transport* tr_)
+        : g(g_), res(res_), bt(bt_), tm(tm_), level_ctr(level_ctr_), tr(tr_), want_type(want_type_),
+          maxd(max_depth < 0 ? INT32_MAX : max_depth), front_atoms(seed_atoms.size()) {
+        pool.t.reserve(24), tmp.t.reserve(8);
+        vis = (u64*)pool.take(row_bytes);
+        lf = (MODE == kSym) ? (u64*)pool.take(sizeof(u64) * (size_t)std::max<int64_t>(M, 1) * W) : nullptr;
+        const size_t hubacc_bytes = sizeof(u64) * (size_t)std::max<int64_t>(g->n_heavy, 1) * W;
+        hubacc = (u64*)pool.take(hubacc_bytes);
+        ever = (u64*)pool.take(bm_bytes);
+        full = (u64*)pool.take(bm_bytes);
+        la = (u64*)pool.take(la_bytes);
+        if constexpr (MODE == kSym && Lay<W>::G >= 4)
+            hm_ok = g->hub_mask != 0 && !tr && !g->shard && g->n_chunks > 0;
+        if (hm_ok) {
+            hm = (u64*)pool.take(hm_bytes);
+            hm_fr = (u64*)pool.take(2 * bm_bytes);
+            hm_lr = (u64*)pool.take(la_bytes);
+        }
+        ctr = (u64*)pool.take(sizeof(u64) * kCtrBlock * max_levels_cap);
+        int32_t* d_atoms = (int32_t*)pool.take(sizeof(int32_t) * seed_atoms.size());
+        u64* d_rows = (u64*)pool.take(sizeof(u64) * seed_rows.size());
+        // one pinned region: two levels' counters in flight, then the seed atoms and rows going up (a copy
+        // from pageable memory is staged by the runtime and holds the host)
+        const size_t o_atoms = sizeof(u64) * kCtrBlock * 2;
+        const size_t o_rows = (o_atoms + sizeof(int32_t) * seed_atoms.size() + 15) & ~(size_t)15;
+        char* hp = (char*)g->pinned_buf(o_rows + sizeof(u64) * seed_rows.size());
+        std::memcpy(hp + o_atoms, seed_atoms.data(), sizeof(int32_t) * seed_atoms.size());
+        std::memcpy(hp + o_rows, seed_rows.data(), sizeof(u64) * seed_rows.size());
+
+        // the prologue's buffers cleared by one launch; level counter blocks (and push-level count rows)
+        // are cleared kZeroLevels at a time as the traversal reaches them
+        bt.lvl.push_back((u64*)g->alloc(row_bytes));
+        bt.fa.push_back((u64*)g->alloc(bm_bytes));
+        if (sparse_ok) {
+            lcand = (u64*)pool.take(la_bytes);
+            cand = (u64*)pool.take(bm_bytes);
+            flist = (int32_t*)pool.take(flist_bytes);
+            clist = (int32_t*)pool.take(flist_bytes);
+        }
+        ZeroList z{};
+        if (cand) z.add(cand, bm_bytes);   // the first push level's candidate words (no memset of their own)
+        z.add(ever, bm_bytes);
+        z.add(full, bm_bytes);
+        z.add(bt.fa[0], bm_bytes);
+        z.add(hubacc, hubacc_bytes);
+        if (hm) z.add(hm, hm_bytes);
+        z.add(ctr, sizeof(u64) * kCtrBlock * kZeroLevels);
+        z.add(scratch_slots(), sizeof(u64) * kCtrBlock);
+        if (!tr) {   // per-source counts of push levels, accumulated by their finalise (readout without a pass)
+            bt.pcnt = (u64*)g->alloc(sizeof(u64) * 1024 * kDirectLevels);
+            z.add(bt.pcnt, sizeof(u64) * 1024 * kZeroLevels);
+            bt.direct.assign(kDirectLevels, 0);
+        }
+        z.launch(s);
+        HGX_HIP(hipMemcpyAsync(d_atoms, hp + o_atoms, sizeof(int32_t) * seed_atoms.size(), hipMemcpyHostToDevice, s));
+        HGX_HIP(hipMemcpyAsync(d_rows, hp + o_rows, sizeof(u64) * seed_rows.size(), hipMemcpyHostToDevice, s));
+        const int n = (int)seed_atoms.size();
+        hgx_seed<W><<<grid_for(n, 256, 1 << 20), 256, 0, s>>>(n, d_atoms, d_rows, bt.lvl[0], vis, bt.fa[0], ever, full, fm);
         HGX_CHECK_LAUNCH();
+        // Readout counting next to the traversal (A/B, HGX_COUNT_EAGER=1): a level's rows are final once
+        // it is produced, so its counting pass can run on a second stream while the following levels run.
+        // Measured slower on config 2 (19.36 against 18.66 ms for traversal + readout,
+        // profiles/r02zj_readout_*.log): the passes share HBM and CUs with the dense levels and delay
+        // them by more than they save.  Default: counted at readout time.  Push levels count their news
+        // in their finalise and need no pass either way.
+        const char* ce = ab_env("HGX_COUNT_EAGER");
+        eager = !tr && !g->shard && ce && ce[0] == '1';
+        if (eager && !g->stream2) {
+            HGX_HIP(hipStreamCreateWithFlags(&g->stream2, hipStreamNonBlocking));
+            HGX_HIP(hipEventCreateWithFlags(&g->ev_count, hipEventDisableTiming));
+        }
+        fuse_ok = !tr && !g->shard && g->count_fused && MODE == kSym && Lay<W>::G >= 4;
+        if (eager) {
+            HGX_HIP(hipEventRecord(g->ev_count, s));
+            count_now(0, g->ev_count);
+        }
+        // Direction choice per level (Beamer-style): when the frontier's incidence volume
+        // sum_{v in F} |inc(v)| is small, the level runs sparse -- candidate links are pushed from the
+        // frontier atoms and only candidate tiles are gathered / pulled.  Otherwise every tile is scanned.
+        if (tr && tr->world > 1) ex.reset(new Exchange(g, tr, W));
+        fl = flist, cl = clist;
+        n_fl = scratch_slots() + 10, n_cl = n_fl + 1, ticket = n_fl + 2;
+        if (!g->ctr_host) {       // two level slots + the seed-volume slot of mapped, coherent host memory
+            void* hp = nullptr;  // (once per graph)
+            HGX_HIP(hipHostMalloc(&hp, sizeof(u64) * 3 * kHostSlot, hipHostMallocMapped | hipHostMallocCoherent));
+            std::memset(hp, 0, sizeof(u64) * 3 * kHostSlot);
+            g->ctr_host = (u64*)hp;
+        }
+        if (!g->pend_ev[0])   // the two in-flight levels' events (once per graph)
+            for (int k = 0; k < 2; ++k) HGX_HIP(hipEventCreateWithFlags(&g->pend_ev[k], hipEventDisableTiming));
+        cand_clean = cand != nullptr;
+        if (sparse_ok) {
+            u64* slot = g->ctr_host + 2 * kHostSlot;
+            const u64 seq = ++g->ctr_seq;
+            __atomic_store_n(slot + 1, (u64)0, __ATOMIC_RELEASE);
+            hgx_seed_degree_host<<<1, 256, 0, s>>>((int32_t)seed_atoms.size(), d_atoms, g->inc_off, slot, seq);
+            HGX_CHECK_LAUNCH();
+            wait_host_word(slot + 1, seq, s, "batched BFS: seed volume never arrived");
+            push_volume = __atomic_load_n(slot, __ATOMIC_RELAXED);
+            push_volume_nf = push_volume;
+        }
+        // HGX_SPARSE_SCALE (A/B builds): multiplies the push / dense threshold (M / 16 incidence entries)
+        static const double kSparseScale = [] {
+            const char* e = ab_env("HGX_SPARSE_SCALE");
+            const double v = e ? std::atof(e) : 1.0;
+            return v > 0 ? v : 1.0;
+        }();
+        sparse_limit = (u64)std::max<int64_t>((int64_t)((double)(M / 16) * kSparseScale), 1024);
+        nf_eligible = sparse_ok && MODE == kSym && Lay<W>::G >= 4 && !ex && (g->bfs_flags & kNfLate);
+        while ((int64_t)nf_stride * 2 * kNfSampleAtoms <= A) nf_stride *= 2;
+        u64* h_sh = (u64*)hp;
+        for (int k = 0; k < 2; ++k) {
+            pend[k].h = h_sh + (size_t)k * kCtrBlock;
+            pend[k].ev = g->pend_ev[k];
+        }
+        cur_lvl = bt.lvl[0];
+        cur_fa = bt.fa[0];
+        pipe_ok = sparse_ok && !ex && MODE != kSym && (g->bfs_flags & kPipePush);
     }
-    // Readout counting next to the traversal (A/B, HGX_COUNT_EAGER=1): a level's rows are final once
-    // it is produced, so its counting pass can run on a second stream while the following levels run.
-    // Measured slower on config 2 (19.36 against 18.66 ms for traversal + readout,
-    // profiles/r02zj_readout_*.log): the passes share HBM and CUs with the dense levels and delay
-    // them by more than they save.  Default: counted at readout time.  Push levels count their news
-    // in their finalise and need no pass either way.
-    const char* ce = ab_env("HGX_COUNT_EAGER");
-    const bool eager = !tr && !g->shard && ce && ce[0] == '1';
-    if (eager && !g->stream2) {
-        HGX_HIP(hipStreamCreateWithFlags(&g->stream2, hipStreamNonBlocking));
-        HGX_HIP(hipEventCreateWithFlags(&g->ev_count, hipEventDisableTiming));
-    }
-    auto count_now = [&](size_t lev, hipEvent_t after) {   // level lev of bt: its counting pass on stream2
-        if (!eager) return;
-        if (lev < bt.direct.size() && bt.direct[lev]) return;
-        if (lev < bt.cpart.size() && bt.cpart[lev]) return;   // counted by the kernels that wrote it
+
+    void count_now(size_t lev, hipEvent_t after) {   // level lev of bt: its counting pass on stream2
+        // (not a level counted by its finalise or by the kernels that wrote it)
+        if (!eager || (lev < bt.direct.size() && bt.direct[lev]) || (lev < bt.cpart.size() && bt.cpart[lev])) return;
         const int cgrid = count_grid(A);
         bt.set_cpart(lev, nullptr, cgrid);
         bt.cpart[lev] = (uint32_t*)g->alloc(bt.cpart_bytes(lev));
         HGX_HIP(hipStreamWaitEvent(g->stream2, after, 0));
         hgx_count_rows<W><<<cgrid, 256, 0, g->stream2>>>(A, bt.fa[lev], nullptr, bt.lvl[lev], bt.cpart[lev]);
         HGX_CHECK_LAUNCH();
-    };
-    // Fused level counts (HGX_OPT_COUNT_FUSED, whole-graph batches as for pcnt): the symmetric-mode
-    // kernels of rows of >= 8 words (more than 256 sources) that store a level's new rows (hgx_atom_pull2 + hgx_hub_finalize,
-    // hgx_nf_pull) count them into block partials; every other level kind is counted at readout.
-    // The LDS planes hold < 2^kFusePlanes rows per workgroup: a workgroup of the pull sees at most
-    // ceil(tiles / waves) * 256 rows, one of the hub finalise or the non-full pull at most
-    // ceil(atoms / groups) * (256 / G) -- about A / 4096 + 256 at the full grids, < 2^20 for any
-    // int32 atom count; fuse_rows_ok checks the actual grids.
-    auto fuse_rows_ok = [](int64_t items, int grid, int per_block) {
-        return ceil_div(items, (int64_t)grid * per_block) * per_block < ((int64_t)1 << kFusePlanes);
-    };
-    const bool fuse_ok = !tr && !g->shard && g->count_fused && MODE == kSym && Lay<W>::G >= 4;
-    if (eager) {
-        HGX_HIP(hipEventRecord(g->ev_count, s));
-        count_now(0, g->ev_count);
     }
 
-    const int block = 256;
-    const int gather_grid = grid_for(ceil_div(M, 64) * 64, block, 256 * 16);
-    const int pull_grid = grid_for(ceil_div(A, 64) * 64, block, 256 * 16);
-    const int hub_grid = grid_for(std::max<int64_t>(g->n_heavy, 1) * Lay<W>::G, block, 256 * 16);
-    const int32_t maxd = max_depth < 0 ? INT32_MAX : max_depth;
-
-    // Direction choice per level (Beamer-style): when the frontier's incidence volume
-    // sum_{v in F} |inc(v)| is small, the level runs sparse -- candidate links are pushed from the
-    // frontier atoms and only candidate tiles are gathered / pulled.  Otherwise every tile is scanned.
-    std::unique_ptr<Exchange> ex;   // one part: no ghosts, nothing to exchange
-    if (tr && tr->world > 1) ex.reset(new Exchange(g, tr, W));
-    // push levels: fl = this level's frontier list, cl = its candidates; the finalise turns cl into the
-    // next level's frontier list (chained), so consecutive push levels swap the two
-    int32_t *fl = flist, *cl = clist;
-    u64* n_fl = ctr + (size_t)(max_levels_cap - 1) * kCtrBlock + 10;   // scratch slots
-    u64* n_cl = n_fl + 1;
-    u64* ticket = n_fl + 2;   // the finalise's last-block ticket (re-zeroed by that block)
-    if (!g->ctr_host) {       // two level slots + the seed-volume slot of mapped, coherent host memory
-        void* hp = nullptr;  // (once per graph)
-        HGX_HIP(hipHostMalloc(&hp, sizeof(u64) * 3 * kHostSlot, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(hp, 0, sizeof(u64) * 3 * kHostSlot);
-        g->ctr_host = (u64*)hp;
+    // The kind of level d and its flags.  Launches nothing but the first-use build of the frontier-code records.
+    LevelPlan plan(int32_t d) {
+        LevelPlan pl{};
+        const bool spec = npend > 0;   // issued before the previous level's counters were read
+        const bool sparse = spec || (sparse_ok && push_volume < sparse_limit);
+        pl.lflags = g->bfs_flags;
+        if ((pl.lflags & kSkipFullLate) && (int64_t)full_total * 16 < A) pl.lflags &= ~kSkipFull;   // adaptive full skip
+        const int lflags = pl.lflags;
+        const bool opush = sparse && (MODE != kSym || (lflags & kSymPush));
+        // late dense level with few atoms left unfull: those pull from the frontier directly
+        bool nfp = !sparse && sparse_ok && MODE == kSym && Lay<W>::G >= 4 && !ex && (lflags & kNfLate) &&
+                   (lflags & kSkipFull) && 4 * (int64_t)(I_total - full_deg_total) < I_total;
+        // ... or an earlier dense level whose listed atoms are predicted to cover after a few rows:
+        // the frontier's rows hold a share p of their bits, so about ln S / -ln(1 - p) independent rows
+        // cover S traversals, each at 1 + 2 / k transactions (k = arity - 1 frontier rows per entry and its
+        // two CSR lines); gather + pull costs the frontier's pins, a row per link and a row per entry
+        pl.nf_late = nfp;   // chosen by the old rule
+        if (!nfp && !sparse && nf_eligible && nf_opt == 2) nfp = true;
+        if (!nfp && !sparse && nf_eligible && nf_opt == 1 && samp_rows > 0 && samp_bits > 0) {
+            const double S = (double)bt.S, pbits = std::min(samp_bits / (samp_rows * S), 0.999);
+            const double need = std::log(S) / -std::log1p(-pbits);
+            const double k = std::max((double)g->P / (double)std::max<int64_t>(M, 1) - 1.0, 1.0);
+            const double I_nf = (double)(I_total - full_deg_total);
+            const double direct = std::min(samp_nf * nf_stride * need * (1.0 + 2.0 / k), I_nf * (k + 2.0));
+            const double old_cost = std::min((double)push_volume_nf, (double)g->P) + (double)M + I_nf;
+            nfp = direct < old_cost;
+            if (trace)
+                std::fprintf(stderr, "[hgx bfs] level %d direct-pull rule: p %.4f need %.1f listed %.0f direct %.3g "
+                             "gather+pull %.3g -> %d\n", d, pbits, need, samp_nf * nf_stride, direct, old_cost, (int)nfp);
+        }
+        // dense level over a frontier whose rows fit the Infinity Cache: the frontier-code pull (bit 17)
+        if (!nfp && !sparse && MODE == kSym && Lay<W>::G >= 4 && !ex && (lflags & kFc) &&
+            (double)front_atoms * W * 8.0 <= kFcFrontBytes)
+            pl.fcrec = ensure_fc_records(g, s);
+        pl.kind = pl.fcrec ? kLvFcPull : nfp ? kLvDirectPull : sparse ? (opush ? kLvPush : kLvSparseGather) : kLvDense;
+        return pl;
     }
-    if (!g->pend_ev[0])   // the two in-flight levels' events (once per graph)
-        for (int k = 0; k < 2; ++k) HGX_HIP(hipEventCreateWithFlags(&g->pend_ev[k], hipEventDisableTiming));
-    // cand was cleared by the prologue launch, and so were the scratch slots n_fl / n_cl (until a level
-    // uses them): the first push level issues no memset (each costs a host API call, ~20 us between
-    // the prologue's device operations on config 5)
-    bool chained = false, cand_clean = cand != nullptr, scratch_clean = true;
-    const bool trace = trace_env("HGX_BFS_TRACE");   // per-level counters to stderr
-    const int64_t I_total = g->I;
-    int64_t full_deg_total = 0;   // sum of |inc(v)| over the atoms visited by every traversal
-    u64 push_volume = 0, push_volume_nf = 0;   // frontier incidence volume (all / not yet full atoms)
-    u64 front_atoms = seed_atoms.size();       // atoms of the current level's frontier
-    if (sparse_ok) {
-        u64* slot = g->ctr_host + 2 * kHostSlot;
-        const u64 seq = ++g->ctr_seq;
-        __atomic_store_n(slot + 1, (u64)0, __ATOMIC_RELEASE);
-        hgx_seed_degree_host<<<1, 256, 0, s>>>((int32_t)seed_atoms.size(), d_atoms, g->inc_off, slot, seq);
+
+    // Frontier-code pull (kLvFcPull).
+    void issue_fc_pull(const LevelPlan& pl, Pend& pn) {
+        const int64_t nwords = ceil_div(A, 64);
+        const int64_t cap = std::max<int64_t>((int64_t)front_atoms, 1);
+        const size_t fw_bytes = sizeof(u64x2) * (size_t)std::max<int64_t>(nwords, 1);
+        const size_t drow_bytes = sizeof(u64) * (size_t)kFcDenseCap * W;
+        u64x2* fwd = (u64x2*)tmp.take(fw_bytes);
+        u64* fcode = (u64*)tmp.take(sizeof(u64) * (size_t)cap);
+        u64* drow = (u64*)tmp.take(drow_bytes);
+        const hgx_graph* root = g->base ? g->base : g;
+        const int32_t n_hubs = root->fc_nhubs;
+        u64* hubtab = (u64*)tmp.take(sizeof(u64) * (size_t)std::max<int32_t>(n_hubs, 1));
+        u64* n_slots = scratch_slots() + 8;
+        unsigned int* n_dense = (unsigned int*)(n_slots + 1);
+        Events e1 = tm.start(kKindFc, pn.d);
+        HGX_HIP(hipMemsetAsync(n_slots, 0, 2 * sizeof(u64), s));
+        hgx_fc_slots<<<grid_for(nwords, 256, 2048), 256, 0, s>>>(nwords, cur_fa, fwd, n_slots);
         HGX_CHECK_LAUNCH();
-        for (unsigned spin = 0; __atomic_load_n(slot + 1, __ATOMIC_ACQUIRE) != seq; ++spin) {
-            if ((spin & 1023u) != 1023u) continue;   // the stream is asked every 1024 polls
-            const hipError_t e = hipStreamQuery(s);
-            if (e == hipErrorNotReady) continue;
-            if (e != hipSuccess) HGX_HIP(e);
-            if (__atomic_load_n(slot + 1, __ATOMIC_ACQUIRE) != seq) fail(HGX_E_DEVICE, "batched BFS: seed volume never arrived");
+        hgx_fc_codes<W><<<grid_for(A, 256, 8192), 256, 0, s>>>(A, fwd, cur_lvl, fcode, cap, drow, n_dense, pn.c);
+        HGX_CHECK_LAUNCH();
+        if (n_hubs > 0) {
+            hgx_fc_hubs<<<grid_for(n_hubs, 256, 64), 256, 0, s>>>(n_hubs, root->fc_hubs, fwd, fcode, hubtab);
+            HGX_CHECK_LAUNCH();
         }
-        push_volume = __atomic_load_n(slot, __ATOMIC_RELAXED);
-        push_volume_nf = push_volume;
+        hgx_fc_pull<W><<<grid_for(ceil_div(A, kFcTile) * 256, 256, 4096), 256, 0, s>>>(
+            A, g->inc_off, pl.fcrec, g->inc_type, want_type, fwd, fcode, drow, hubtab, n_hubs, cur_lvl, vis, ever,
+            full, pn.lvl_next, pn.fa_next, pn.c, fm, pl.lflags);
+        HGX_CHECK_LAUNCH();
+        tm.stop(e1);
+        if (g->n_chunks > 0) {
+            Events e3 = tm.start(kKindFcHeavy, pn.d);
+            hgx_fc_pull_heavy<W><<<(unsigned)g->n_chunks, 256, 0, s>>>(g->chunks, pl.fcrec, g->inc_type, want_type,
+                fwd, fcode, drow, hubtab, n_hubs, cur_lvl, vis, ever, full, hubacc, pn.c, fm, pl.lflags);
+            HGX_CHECK_LAUNCH();
+            tm.stop(e3);
+            Events e4 = tm.start(kKindHub, pn.d);
+            hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis,
+                                                           ever, full, pn.lvl_next, pn.fa_next, pn.c, fm, nullptr);
+            HGX_CHECK_LAUNCH();
+            tm.stop(e4);
+        }
+        tmp.give_back();   // stream-ordered reuse
     }
-    // HGX_SPARSE_SCALE (A/B builds): multiplies the push / dense threshold (M / 16 incidence entries)
-    static const double kSparseScale = [] {
-        const char* e = ab_env("HGX_SPARSE_SCALE");
-        const double v = e ? std::atof(e) : 1.0;
-        return v > 0 ? v : 1.0;
-    }();
-    const u64 sparse_limit = (u64)std::max<int64_t>((int64_t)((double)(M / 16) * kSparseScale), 1024);
-    // Full-visited skipping costs two bitmap probes per pin; it pays once a sizeable share of the
-    // atoms is visited by every traversal (seeds that are full count from the start).
-    u64 full_total = 0;
 
-    struct Pend {
-        int32_t d = 0;
-        u64* lvl_next = nullptr;
-        u64* fa_next = nullptr;
-        int kind = 0, allrows = 0;
-        u64 new_global = 0, part_push = 0;
-        u64* h = nullptr;
-        hipEvent_t ev = nullptr;
-        bool flag = false;    // counters in slot[0..cNum) once slot[cNum] == seq (mapped host memory)
-        u64 seq = 0;
-        u64* slot = nullptr;
-        uint32_t* cpart = nullptr;   // fused counts of the level's new rows: cblk block partials
-        int32_t cblk = 0;
-        bool sampled = false;   // hgx_level_sample ran: cDirRows / cScanned carry its sample
-    } pend[2];
-    // The direct-pull rule (HGX_OPT_NF_PULL = 1): the sample of the previous level
-    const int nf_opt = g->nf_pull;
-    const bool nf_eligible = sparse_ok && MODE == kSym && Lay<W>::G >= 4 && !ex && (g->bfs_flags & 256);
-    int nf_stride = 1;
-    while ((int64_t)nf_stride * 2 * kNfSampleAtoms <= A) nf_stride *= 2;
-    double samp_rows = 0, samp_bits = 0, samp_nf = 0;   // (zero: no sample, the rule does not select)
-    auto cpart_size = [](int32_t blocks) { return sizeof(uint32_t) * (size_t)blocks * W * 64; };
-    for (int k = 0; k < 2; ++k) {
-        pend[k].h = h_sh + (size_t)k * kCtrBlock;
-        pend[k].ev = g->pend_ev[k];
-    }
-    int npend = 0;
-    bool stop = false;
-    u64* cur_lvl = bt.lvl[0];
-    u64* cur_fa = bt.fa[0];
-    const bool pipe_ok = sparse_ok && !ex && MODE != kSym && (g->bfs_flags & 512);
-    // End-of-level wait: a host spin (the blocking wait adds tens of microseconds per level, and
-    // unbounded traversals run tens of short levels).
-    auto wait_event = [](hipEvent_t ev) {
-        hipError_t e;
-        while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
+    // Direct pull (kLvDirectPull): the atoms not yet visited by every traversal, listed, pull from the frontier
+    // rows; with the hint step first, and the hubs' rest through the chunk kernel and the hub finalise.
+    void issue_direct_pull(const LevelPlan& pl, Pend& pn) {
+        Events e2 = tm.start(kKindNf, pn.d);
+        HGX_HIP(hipMemsetAsync(pn.fa_next, 0, bm_bytes, s));
+        u64* n_list = scratch_slots() + 8;
+        u64* n_rlist = n_list + 1;   // (the residual list's)
+        HGX_HIP(hipMemsetAsync(n_list, 0, 2 * sizeof(u64), s));
+        // the hint step: only where a co-target of any incident link is certainly a neighbour
+        const bool hinted = g->nf_hint == 1 && nf_opt != 0 && want_type < 0;
+        if (hinted) ensure_nbr_hint(g, s);
+        ensure_hasinc(g, s);
+        const u64* hasinc = (const u64*)g->hasinc;
+        hgx_nonfull_list<<<grid_for(ceil_div(A, 64), 256, 2048), 256, 0, s>>>(A, full, hasinc, clist, n_list);
+        HGX_CHECK_LAUNCH();
+        constexpr int nf_grid = 4096, G = Lay<W>::G;
+        // the cover test's step in entries (DESIGN 3.1 item 12 has the steps measured): with
+        // HGX_OPT_NF_PULL = 0 the group's G entries; else 2 where the rule (or value 2) chose the
+        // level, 1 on the late levels of the old rule; HGX_NF_E overrides (A/B builds)
+        const int nf_e = nf_opt == 0 ? G : ab_int("HGX_NF_E", pl.nf_late ? 1 : 2);
+        const bool stepped = nf_e == 1 || nf_e == 2 || (nf_e == 4 && G > 4);   // hgx_nf_pull_e
+        // hubs: hgx_nf_pull_e leaves those not covered by their first kHeavyDegree entries to the
+        // chunk kernel and the hub finalise (whose blocks own the partial rows after the pull's)
+        const bool hubs = stepped && g->n_chunks > 0;
+        // The hint step's blocks own the partial rows after those..  Its grid: the workgroups the device holds at
+        // once (2048 ran a second, partly filled round: + 0.17 ms on config 2's level 2; HGX_NF_HINT_GRID: A/B
+        // builds), 256 at least -- a block then stores at most ceil(A / (256 * chunk)) * chunk rows, below
+        // 2^kFusePlanes for any int32 atom count, so the level is fused with the hint exactly when it is without.
+        static const int hint_resident = [&] {
+            int per_cu = 0, cus = 0;
+            HGX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hgx_nf_hint<W>, 256, 0));
+            HGX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
+            return std::min(std::max(per_cu * cus, 256), 4096);
+        }();
+        const int hint_grid = hinted ? std::max(ab_int("HGX_NF_HINT_GRID", hint_resident), 256) : 0;
+        if (fuse_ok && fuse_rows_ok(A, nf_grid, 256 / G) &&
+            (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / G)) &&
+            (!hinted || fuse_rows_ok(A, hint_grid, kNfHintChunk))) {
+            pn.cblk = nf_grid + (hubs ? hub_grid : 0) + hint_grid;
+            pn.cpart = (uint32_t*)g->alloc(cpart_size(pn.cblk));
         }
-        HGX_HIP(e);
-    };
-    // One level's counters -> host state; false once the level found no new atom (its rows released).
-    auto read_level = [&](Pend& p) -> bool {
-        if (p.flag) {   // spin on the sequence word; a stream that finished or failed without it is an error
-            for (unsigned spin = 0; __atomic_load_n(p.slot + cNum, __ATOMIC_ACQUIRE) != p.seq; ++spin) {
-                if ((spin & 1023u) != 1023u) continue;   // the stream is asked every 1024 polls
-                const hipError_t e = hipStreamQuery(s);
-                if (e == hipErrorNotReady) continue;
-                if (e != hipSuccess) HGX_HIP(e);
-                if (__atomic_load_n(p.slot + cNum, __ATOMIC_ACQUIRE) != p.seq)
-                    fail(HGX_E_DEVICE, "batched BFS: level counters never arrived");
+        const int32_t* nf_list = clist;
+        const u64* nf_n = n_list;
+        if (hinted) {   // the atoms their hint row covers are written here, the rest listed again
+            hgx_nf_hint<W><<<hint_grid, 256, 0, s>>>(
+                clist, n_list, g->nbr_hint, g->inc_off, cur_fa, cur_lvl, vis, ever, full, pn.lvl_next, pn.fa_next, pn.c, fm,
+                pn.cpart ? pn.cpart + (size_t)(pn.cblk - hint_grid) * W * 64 : nullptr, flist, n_rlist);
+            HGX_CHECK_LAUNCH();
+            nf_list = flist;
+            nf_n = n_rlist;
+        }
+        u64* resid = nullptr;
+        if (hubs) {
+            resid = (u64*)tmp.take(bm_bytes);
+            HGX_HIP(hipMemsetAsync(resid, 0, bm_bytes, s));
+        }
+#define HGX_NF_ARGS nf_list, nf_n, g->inc_off, g->inc_row, g->inc_type, want_type, g->tgt_off, g->tgt_idx, cur_fa, cur_lvl, vis, \
+                ever, full, pn.lvl_next, pn.fa_next, pn.c, fm, pl.lflags, pn.cpart
+        // (a test per entry with 8 atoms in flight spills: 4 entry slots there)
+        if (nf_e == 1) hgx_nf_pull_e<W, 1, 4><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
+        else if (nf_e == 2) hgx_nf_pull_e<W, 2, G><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
+        else if (stepped) hgx_nf_pull_e<W, G / 2, G><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
+        else hgx_nf_pull<W><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS);
+#undef HGX_NF_ARGS
+        HGX_CHECK_LAUNCH();
+        if (hubs) {
+            const int hgrid = (int)std::min<int64_t>(g->n_chunks, 2048);
+            hgx_nf_pull_heavy<W><<<hgrid, 256, 0, s>>>(g->chunks, g->n_chunks, resid, g->inc_row, g->inc_type,
+                want_type, g->tgt_off, g->tgt_idx, cur_fa, cur_lvl, vis, ever, hubacc, pn.c, fm, pl.lflags);
+            HGX_CHECK_LAUNCH();
+            hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis, ever,
+                full, pn.lvl_next, pn.fa_next, pn.c, fm, pn.cpart ? pn.cpart + (size_t)nf_grid * W * 64 : nullptr);
+            HGX_CHECK_LAUNCH();
+            tmp.give_back();   // stream-ordered reuse
+        }
+        tm.stop(e2);
+    }
+
+    // Frontier-driven push (kLvPush: mark candidates, zero their rows, OR rows, finalise): the ordered
+    // modes always, the symmetric mode with HGX_OPT_BFS_FLAGS bit 5
+    void issue_push(Pend& pn) {
+        const bool pre_work = !g->zacc_clean || g->zacc_bytes < row_bytes || (MODE != kSym && !g->inc_yf) ||
+                              g->n_pchunks < 0 || !cand_clean || !chained;
+        if (pre_work) tm.break_chain();
+        ensure_zacc(g, row_bytes, s);
+        g->zacc_clean = false;   // until this level's finalise has run
+        u64* acc = (u64*)g->zacc;
+        if (MODE != kSym) ensure_inc_yield(g);
+        const uint8_t* yf = g->inc_yf;
+        ensure_push_chunks(g);
+        // chained levels need no memset: the candidate words are zero-invariant, fa_next is cleared by
+        // hgx_opush and n_cl by the previous finalise
+        if (!cand_clean) HGX_HIP(hipMemsetAsync(cand, 0, bm_bytes, s));
+        if (!chained) {   // the frontier list from the bitmap (else the last finalise left it in fl)
+            if (!scratch_zero) {
+                HGX_HIP(hipMemsetAsync(n_cl, 0, sizeof(u64), s));
+                HGX_HIP(hipMemsetAsync(n_fl, 0, sizeof(u64), s));
             }
+            const int fgrid = grid_for(ceil_div(A, 64), 256, 256);   // <= 256 list atomics per level
+            hgx_frontier_list<<<fgrid, 256, 0, s>>>(A, cur_fa, g->inc_off, fl, n_fl, kPushLight);
+            HGX_CHECK_LAUNCH();
+        }
+        // 2048 waves grid-striding over the frontier list: config 5 levels of 20 to 35K atoms measured
+        // 19-113 us against 30-142 us with 8192 waves (the launch of mostly idle workgroups and
+        // the candidate-append contention) and 20-171 us with 1024 waves
+        static const int kPushGrid = [] {   // HGX_PUSH_GRID (A/B builds): override of the push grid (blocks)
+            const char* e = ab_env("HGX_PUSH_GRID");
+            const int v = e ? std::atoi(e) : 0;
+            return v >= 64 && v <= 8192 ? v : 512;
+        }();
+        const int lgrid = kPushGrid;
+        Events e2 = tm.start_chained(kKindPush, pn.d);
+        // hub chunks inside hgx_opush while there are few of them (config 5: ~350 chunks, one launch
+        // less per level); a block per chunk in hgx_opush_heavy when there are many (config 2:
+        // ~380K chunks of 26K hubs: folded into 512 blocks the seed level took 0.58 ms against 0.41)
+        const bool fold = g->n_pchunks <= 8 * lgrid;
+        // hub chunks in the same launch when folded
+        hgx_opush<W, MODE><<<lgrid, 256, 0, s>>>(fl, n_fl, g->inc_off, g->inc_row, g->inc_type, want_type, yf,
+            g->tgt_off, g->tgt_idx, cur_lvl, full, cand, cl, n_cl, acc, pn.c, pn.fa_next,
+            (int64_t)(bm_bytes / sizeof(u64)), g->pchunks, fold ? g->n_pchunks : 0, cur_fa);
+        HGX_CHECK_LAUNCH();
+        if (!fold && g->n_pchunks > 0) {
+            hgx_opush_heavy<W, MODE><<<(unsigned)g->n_pchunks, 256, 0, s>>>(g->pchunks, cur_fa, g->inc_row, g->inc_type,
+                want_type, yf, g->tgt_off, g->tgt_idx, cur_lvl, full, cand, cl, n_cl, acc, pn.c);
+            HGX_CHECK_LAUNCH();
+        }
+        // finalise; re-zeroes the accumulator rows and candidate words it consumed and, without a ghost exchange,
+        // rewrites the candidate list into the next level's frontier list without an exchange the level's counters go
+        // straight to mapped host memory (no copy in the stream between this level and the next)
+        if (!ex) {
+            pn.flag = true;
+            pn.seq = ++g->ctr_seq;
+            pn.slot = g->ctr_host + (size_t)(pn.d & 1) * kHostSlot;
+            __atomic_store_n(pn.slot + cNum, (u64)0, __ATOMIC_RELEASE);
+        }
+        u64* lcount = nullptr;   // the new level's counts accumulated by the finalise (no exchange)
+        if (!ex && bt.pcnt && pn.d + 1 < kDirectLevels) {
+            lcount = bt.pcnt + (size_t)(pn.d + 1) * 1024;
+            bt.direct[pn.d + 1] = 1;
+        }
+        hgx_push_finalize_list<W><<<512, 256, 0, s>>>(cl, n_cl, g->inc_off, acc, cand, vis, ever, full, pn.lvl_next,
+            pn.fa_next, pn.c, fm, ex ? 0 : 1, ex ? nullptr : n_fl, ticket, pn.flag ? pn.slot : nullptr, pn.seq, lcount);
+        HGX_CHECK_LAUNCH();
+        g->zacc_clean = true;   // every accumulated row is in the candidate list and re-zeroed
+        cand_clean = true;
+        chained = !ex;
+        std::swap(fl, cl);
+        std::swap(n_fl, n_cl);
+        tm.stop_chained(e2);
+    }
+
+    // Sparse gather (kLvSparseGather, symmetric mode): the frontier's links are marked and gathered, their lf
+    // rows pushed into the candidate atoms (candidates are few, hubs must not be re-scanned).
+    void issue_sparse_gather(const LevelPlan& pl, Pend& pn) {
+        Events e0 = tm.start(kKindGather, pn.d);
+        HGX_HIP(hipMemsetAsync(lcand, 0, la_bytes, s));
+        HGX_HIP(hipMemsetAsync(cand, 0, bm_bytes, s));
+        hgx_frontier_links<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(
+            A, cur_fa, g->inc_off, g->inc_row, g->link_type, want_type, lcand);
+        HGX_CHECK_LAUNCH();
+        if (g->n_chunks > 0) {
+            hgx_frontier_links_heavy<<<(unsigned)g->n_chunks, 256, 0, s>>>(g->chunks, cur_fa, g->inc_row,
+                                                                         g->link_type, want_type, lcand);
+            HGX_CHECK_LAUNCH();
+        }
+        tm.stop(e0);
+        Events e1 = tm.start(kKindGather, pn.d);
+        hgx_link_gather<W, MODE == kSym><<<gather_grid, block, 0, s>>>(M, g->tgt_off, g->tgt_idx, g->link_type,
+            want_type, cur_fa, full, cur_lvl, lf, la, pn.c, fm, pl.lflags, lcand, cand);
+        HGX_CHECK_LAUNCH();
+        tm.stop(e1);
+        Events e2 = tm.start(kKindPull, pn.d);
+        hgx_push_zero<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(A, W, cand, full, pn.lvl_next);
+        HGX_CHECK_LAUNCH();
+        hgx_push_rows<<<grid_for(ceil_div(M, 64) * 64, 256, 4096), 256, 0, s>>>(M, W, la, g->tgt_off, g->tgt_idx,
+                                                                             lf, full, pn.lvl_next);
+        HGX_CHECK_LAUNCH();
+        hgx_push_finalize<W><<<pull_grid, block, 0, s>>>(A, g->inc_off, cand, vis, ever, full, pn.lvl_next, pn.fa_next,
+                                                         pn.c, fm);
+        HGX_CHECK_LAUNCH();
+        tm.stop(e2);
+    }
+
+    // Dense level (kLvDense): every link gathers its frontier targets' rows into lf, every atom pulls its links' lf
+    // rows (hubs by chunks into hubacc, then the hub finalise); with the hub mask a chunk that covers C reads on by lr.
+    void issue_dense(const LevelPlan& pl, Pend& pn) {
+        int lflags = pl.lflags;
+        const bool v2 = Lay<W>::G >= 4 && !(lflags & kOneRowDense);   // MLP-restructured dense kernels
+        // A frontier whose incidence volume covers the links twice leaves few links inactive: the
+        // gather then writes a (zero) row for every link and the pull reads rows without probing la
+        // -- one dependent load fewer per incidence chunk (HGX_OPT_BFS_FLAGS bit 7).
+        if (v2 && (lflags & kAllRowsOpt) && MODE == kSym && push_volume_nf >= 2 * (u64)M) lflags |= kAllRows;
+        pn.allrows = (lflags & kAllRows) ? 1 : 0;
+        // hub mask: an all-rows level of the MLP kernels
+        bool hmask = false;
+        u64* hm_slot = nullptr;
+        const u64 hm_limit = (u64)(g->I_heavy / 4);
+        const int hm_S = (int)bt.S;
+        if constexpr (MODE == kSym && Lay<W>::G >= 4) {
+            // (hgx_hub_mask reads every frontier row: under the rule only while the frontier is at most half of the atoms)
+            hmask = hm_ok && v2 && (lflags & kAllRows) && !(lflags & (kGatherO5 | kHeavyMlp2)) &&
+                    (g->hub_mask == 2 || front_atoms * 2 <= (u64)A);
+            if (hmask) {   // C, fr and the rule's counters first (the frontier is final)
+                ensure_top_list(g, s);   // once per snapshot
+                hm_slot = hm + (size_t)(hm_levels & 1) * kHmSlot;
+                Events e0 = tm.start(kKindGather, pn.d);
+                hgx_hub_mask<W><<<grid_for(ceil_div(A, 64), 256, 2048), 256, 0, s>>>(
+                    A, g->top_list, std::min(g->hub_mask_t, g->top_n), cur_fa, cur_lvl, g->inc_off, hm + 2 * kHmSlot, hm_fr,
+                    hm_slot, hm + (size_t)((hm_levels + 1) & 1) * kHmSlot);
+                HGX_CHECK_LAUNCH();
+                tm.stop(e0);
+                ++hm_levels;
+                if (trace) {   // the rule's inputs (a host wait: tracing only)
+                    u64 h[kHmSlot + 16];
+                    HGX_HIP(hipMemcpyAsync(h, hm_slot, sizeof(u64) * kHmSlot, hipMemcpyDeviceToHost, s));
+                    HGX_HIP(hipMemcpyAsync(h + kHmSlot, hm + 2 * kHmSlot, sizeof(u64) * 16, hipMemcpyDeviceToHost, s));
+                    HGX_HIP(hipStreamSynchronize(s));
+                    u64 fdeg = 0, pc = 0;
+                    for (int k = 0; k < kStatShards; ++k) fdeg += h[k * kStatStride + kHmDeg];
+                    for (int w = 0; w < W; ++w) pc += (u64)__builtin_popcountll(h[kHmSlot + w]);
+                    std::fprintf(stderr, "[hgx bfs] level %d hub mask: T %d listed on the frontier %llu |C| %llu (row %llu) "
+                                 "fr degree sum %llu limit %llu\n", pn.d, std::min(g->hub_mask_t, g->top_n),
+                                 (unsigned long long)h[kHmListed], (unsigned long long)h[kHmPop], (unsigned long long)pc,
+                                 (unsigned long long)fdeg, (unsigned long long)hm_limit);
+                }
+            }
+        }
+        Events e1 = tm.start(kKindGather, pn.d);
+        if constexpr (MODE == kSym && Lay<W>::G >= 4) {
+            if (hmask)
+                hgx_link_gather2_fr<W><<<gather_grid, block, 0, s>>>(
+                    M, g->tgt_off, g->tgt_idx, g->link_type, want_type, cur_fa, full, cur_lvl, lf, la, pn.c, fm, lflags, hm_fr,
+                    hm_lr, hm_slot, g->hub_mask, hm_S, hm_limit);
+        }
+        if constexpr (Lay<W>::G >= 4) {
+            if (v2 && !hmask) {
+                if (lflags & kGatherO5)   // diagnostic A/B (bit 10)
+                    hgx_link_gather2_o5<W, MODE == kSym><<<gather_grid, block, 0, s>>>(
+                        M, g->tgt_off, g->tgt_idx, g->link_type, want_type, cur_fa, full, cur_lvl, lf, la, pn.c, fm, lflags);
+                else
+                    hgx_link_gather2<W, MODE == kSym><<<gather_grid, block, 0, s>>>(
+                        M, g->tgt_off, g->tgt_idx, g->link_type, want_type, cur_fa, full, cur_lvl, lf, la, pn.c, fm, lflags);
+            }
+        }
+        if (!v2)
+            hgx_link_gather<W, MODE == kSym><<<gather_grid, block, 0, s>>>(M, g->tgt_off, g->tgt_idx, g->link_type,
+                want_type, cur_fa, full, cur_lvl, lf, la, pn.c, fm, lflags, nullptr, nullptr);
+        HGX_CHECK_LAUNCH();
+        tm.stop(e1);
+        Events e2 = tm.start(kKindPull, pn.d);
+        if constexpr (Lay<W>::G >= 4 && MODE == kSym) {
+            if (v2) {
+                // two atoms of a group interleaved (152 VGPRs, 3 waves/SIMD): config 2 pull 5.73 -> 5.23 ms
+                // a step against four (184 VGPRs, 2 waves/SIMD, dropped in r02); a tile's atoms placed in
+                // descending degree order (5.20 -> 5.13 ms, profiles/r02r_ab_pull_sort.log).  Bit 11 (A/B):
+                // half of a group's rows in flight at once (fewer VGPRs, more waves per SIMD).
+                // fused counts: the pull's blocks own the first pull_grid partial rows of the level, the hub
+                // finalise's blocks (when the snapshot has hubs) the hub_grid rows after them
+                const bool hubs = g->n_chunks > 0;
+                if (fuse_ok && fuse_rows_ok(ceil_div(A, 64) * 64, pull_grid, block) &&
+                    (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / Lay<W>::G))) {
+                    pn.cblk = pull_grid + (hubs ? hub_grid : 0);
+                    pn.cpart = (uint32_t*)g->alloc(cpart_size(pn.cblk));
+                }
+                if (lflags & kPullHalf)
+                    hgx_atom_pull2<W, 2, true, Lay<W>::G / 2><<<pull_grid, block, 0, s>>>(A, g->inc_off, g->inc_row, la,
+                        lf, vis, ever, full, pn.lvl_next, pn.fa_next, pn.c, fm, lflags, own_bm, pn.cpart);
+                else
+                    hgx_atom_pull2<W, 2, true, Lay<W>::G><<<pull_grid, block, 0, s>>>(A, g->inc_off, g->inc_row, la, lf,
+                        vis, ever, full, pn.lvl_next, pn.fa_next, pn.c, fm, lflags, own_bm, pn.cpart);
+            }
+        }
+        if (!(v2 && MODE == kSym))
+            hgx_atom_pull<W, MODE><<<pull_grid, block, 0, s>>>(A, g->inc_off, g->inc_row, la, lf, g->tgt_off,
+                g->tgt_idx, cur_fa, cur_lvl, vis, ever, full, pn.lvl_next, pn.fa_next, pn.c, fm, lflags, nullptr);
+        HGX_CHECK_LAUNCH();
+        tm.stop(e2);
+        if (g->n_chunks > 0) {
+            Events e3 = tm.start(kKindHeavy, pn.d);
+            if constexpr (MODE == kSym && Lay<W>::G >= 4) {
+                if (hmask)
+                    hgx_atom_pull_hub<W><<<(unsigned)g->n_chunks, block, 0, s>>>(
+                        g->chunks, g->inc_row, la, lf, hm_lr, hm + 2 * kHmSlot, hm_slot, vis, ever, full, hubacc, pn.c, fm,
+                        lflags, g->hub_mask, hm_S, hm_limit, g->hub_mask_sched);
+            }
+            if (!hmask)
+                hgx_atom_pull_heavy<W, MODE><<<(unsigned)g->n_chunks, block, 0, s>>>(g->chunks, g->inc_row, la, lf,
+                    g->tgt_off, g->tgt_idx, cur_fa, cur_lvl, vis, ever, full, hubacc, pn.c, fm, lflags, nullptr);
+            HGX_CHECK_LAUNCH();
+            tm.stop(e3);
+            Events e4 = tm.start(kKindHub, pn.d);
+            hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis, ever,
+                full, pn.lvl_next, pn.fa_next, pn.c, fm, pn.cpart ? pn.cpart + (size_t)pull_grid * W * 64 : nullptr);
+            HGX_CHECK_LAUNCH();
+            tm.stop(e4);
+        }
+    }
+
+    // Level d starts: the next counter blocks cleared when due; its Pend (read two levels ago) with the rows it writes.
+    Pend& begin_level(int32_t d) {
+        if ((d + 1) % kZeroLevels == 0) {   // the next kZeroLevels counter blocks / count rows
+            ZeroList zl{};
+            const int64_t b0 = d + 1, b1 = b0 + kZeroLevels;
+            zl.add(ctr + (size_t)(b0 % ctr_ring) * kCtrBlock, sizeof(u64) * kCtrBlock * (size_t)kZeroLevels);
+            if (bt.pcnt && b0 < kDirectLevels)
+                zl.add(bt.pcnt + (size_t)b0 * 1024, sizeof(u64) * 1024 * (size_t)(std::min<int64_t>(b1, kDirectLevels) - b0));
+            zl.launch(s);
+        }
+        scratch_zero = scratch_clean;
+        scratch_clean = false;
+        Pend& pn = pend[d & 1];
+        pn = Pend{d, nullptr, nullptr, ctr + (size_t)(d % ctr_ring) * kCtrBlock, kLvDense, 0, 0, 0, pn.h, pn.ev};
+        pn.lvl_next = (u64*)g->alloc(row_bytes);
+        pn.fa_next = (u64*)g->alloc(bm_bytes);   // every word written by hgx_atom_pull
+        return pn;
+    }
+
+    // The level is issued: the partition exchange, the sample for the next level's rule, its counters on their way.
+    void close_level(Pend& pn) {
+        const int32_t d = pn.d;
+        if (ex) {
+            double lb = 0, pm = 0;
+            pn.new_global = ex->template level<W>(pn.lvl_next, pn.fa_next, vis, ever, full, fm, &pn.part_push, &lb, &pm,
+                                                  tm, d, d + 1 >= maxd);
+            if (d < 64) {
+                res->stats.level_xbytes[d] += lb;
+                res->stats.level_xpair_max[d] = std::max(res->stats.level_xpair_max[d], pm);
+                res->stats.level_xtrips[d] = std::max(res->stats.level_xtrips[d], (int32_t)ex->trips);
+            }
+        }
+        // a dense level's sample for the next level's direct-pull rule
+        pn.sampled = !pn.flag && pn.kind != kLvPush && pn.kind != kLvSparseGather && nf_eligible && nf_opt == 1 &&
+                     d + 1 < maxd;
+        if (pn.sampled) {
+            hgx_level_sample<W><<<grid_for(ceil_div(A, nf_stride), 256, 4096), 256, 0, s>>>(
+                A, nf_stride, pn.fa_next, pn.lvl_next, full, g->inc_off, pn.c);
+            HGX_CHECK_LAUNCH();
+        }
+        if (!pn.flag) {
+            tm.break_chain();
+            HGX_HIP(hipMemcpyAsync(pn.h, pn.c, sizeof(u64) * kCtrBlock, hipMemcpyDeviceToHost, s));
+            HGX_HIP(hipEventRecord(pn.ev, s));
+        }
+        ++npend;
+        cur_lvl = pn.lvl_next;
+        cur_fa = pn.fa_next;
+    }
+
+    // One level's counters -> host state; false once the level found no new atom (its rows released).
+    bool read_level(Pend& p) {
+        LevelRec rec;
+        u64* h_new = rec.c;
+        if (p.flag) {   // the finalise's sequence word
+            wait_host_word(p.slot + cNum, p.seq, s, "batched BFS: level counters never arrived");
             for (int k = 0; k < cNum; ++k) h_new[k] = __atomic_load_n(p.slot + k, __ATOMIC_RELAXED);
         } else {
-            wait_event(p.ev);
+            spin_event(p.ev);
             for (int k = 0; k < cNum; ++k) {
                 h_new[k] = 0;
                 for (int sh = 0; sh < kCtrShards; ++sh) h_new[k] += p.h[sh * kCtrStride + k];
@@ -5028,18 +5517,17 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
             h_new[cNewAtoms] = p.new_global;
             h_new[cNewDeg] = p.part_push;
         }
-        u64 hinted = 0;   // hgx_nf_hint packs the atoms it decided above cCand's own count
-        if (p.kind == 3) {
-            hinted = h_new[cCand] >> 32;
+        rec.kind = p.kind;
+        rec.hinted = 0;   // hgx_nf_hint packs the atoms it decided above cCand's own count
+        if (p.kind == kLvDirectPull) {
+            rec.hinted = h_new[cCand] >> 32;
             h_new[cCand] &= 0xffffffffull;
         }
-        level_ctr.push_back(std::vector<u64>(h_new, h_new + cNum));
-        level_ctr.back()[cDirRows] = (u64)p.kind;   // (host-side) kind of this level
-        level_ctr.back().push_back(hinted);         // [cNum]: listed atoms decided by their hint row
+        level_ctr.push_back(rec);
         if (!ex) full_deg_total += (int64_t)(h_new[cNewDeg] - h_new[cNewDegNF]);   // incidence of atoms now full
         if (trace)
             std::fprintf(stderr, "[hgx bfs] level %d kind %d allrows %d active_links %llu new %llu push %llu push_nf %llu "
-                         "new_full %llu\n", p.d, p.kind, p.allrows,
+                         "new_full %llu\n", p.d, (int)p.kind, p.allrows,
                          (unsigned long long)h_new[cActiveLinks], (unsigned long long)h_new[cNewAtoms],
                          (unsigned long long)h_new[cNewDeg], (unsigned long long)h_new[cNewDegNF],
                          (unsigned long long)h_new[cNewFull]);
@@ -5048,506 +5536,25 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
         front_atoms = h_new[cNewAtoms];
         full_total += h_new[cNewFull];
         if (h_new[cNewAtoms] == 0) {
-            g->release(p.lvl_next, row_bytes);
-            g->release(p.fa_next, bm_bytes);
-            if (p.cpart) g->release(p.cpart, cpart_size(p.cblk));
+            drop_rows(p);
             return false;
         }
-        bt.lvl.push_back(p.lvl_next);
+        bt.lvl.push_back(p.lvl_next);   // bt owns them from here on, one by one
+        p.lvl_next = nullptr;
         bt.fa.push_back(p.fa_next);
-        if (p.cpart) bt.set_cpart(bt.lvl.size() - 1, p.cpart, p.cblk);
+        p.fa_next = nullptr;
+        if (p.cpart) {
+            bt.set_cpart(bt.lvl.size() - 1, p.cpart, p.cblk);
+            p.cpart = nullptr;
+        }
         if (!p.flag) count_now(bt.lvl.size() - 1, p.ev);   // p.ev follows the level's kernels
         return true;
-    };
+    }
 
-    for (int32_t d = 0; d < maxd && !stop; ++d) {
-        if ((d + 1) % kZeroLevels == 0) {   // the next kZeroLevels counter blocks / count rows
-            ZeroList zl{};
-            const int64_t b0 = d + 1, b1 = b0 + kZeroLevels;
-            zl.add(ctr + (size_t)(b0 % ctr_ring) * kCtrBlock, sizeof(u64) * kCtrBlock * (size_t)kZeroLevels);
-            if (bt.pcnt && b0 < kDirectLevels)
-                zl.add(bt.pcnt + (size_t)b0 * 1024, sizeof(u64) * 1024 * (size_t)(std::min<int64_t>(b1, kDirectLevels) - b0));
-            zl.launch(s);
-        }
-        u64* lvl = cur_lvl;
-        u64* fa = cur_fa;
-        const bool scratch_zero = scratch_clean;   // first level: n_fl / n_cl still zero from the prologue
-        scratch_clean = false;
-        bool flag_level = false;   // counters written by the finalise into mapped host memory
-        u64 flag_seq = 0;
-        u64* flag_slot = nullptr;
-        const bool spec = npend > 0;   // issued before the previous level's counters were read
-        u64* lvl_next = (u64*)g->alloc(row_bytes);
-        u64* fa_next = (u64*)g->alloc(bm_bytes);   // every word written by hgx_atom_pull
-        u64* c = ctr + (size_t)(d % ctr_ring) * kCtrBlock;
-        uint32_t* lv_cpart = nullptr;   // fused counts of this level's new rows (lv_cblk block partials)
-        int32_t lv_cblk = 0;
-        const bool sparse = spec || (sparse_ok && push_volume < sparse_limit);
-        int lflags = g->bfs_flags;
-        if ((lflags & 16) && (int64_t)full_total * 16 < A) lflags &= ~4;   // adaptive full skip
-        const bool opush = sparse && (MODE != kSym || (lflags & 32));
-        // late dense level with few atoms left unfull: those pull from the frontier directly
-        bool nfp = !sparse && sparse_ok && MODE == kSym && Lay<W>::G >= 4 && !ex && (lflags & 256) &&
-                   (lflags & 4) && 4 * (int64_t)(I_total - full_deg_total) < I_total;
-        // ... or an earlier dense level whose listed atoms are predicted to cover after a few rows:
-        // the frontier's rows hold a share p of their bits, so about ln S / -ln(1 - p) independent rows
-        // cover S traversals, each at 1 + 2 / k transactions (k = arity - 1 frontier rows per entry and its
-        // two CSR lines); gather + pull costs the frontier's pins, a row per link and a row per entry
-        const bool nf_late = nfp;   // chosen by the old rule
-        if (!nfp && !sparse && nf_eligible && nf_opt == 2) nfp = true;
-        if (!nfp && !sparse && nf_eligible && nf_opt == 1 && samp_rows > 0 && samp_bits > 0) {
-            const double S = (double)bt.S, pbits = std::min(samp_bits / (samp_rows * S), 0.999);
-            const double need = std::log(S) / -std::log1p(-pbits);
-            const double k = std::max((double)g->P / (double)std::max<int64_t>(M, 1) - 1.0, 1.0);
-            const double I_nf = (double)(I_total - full_deg_total);
-            const double direct = std::min(samp_nf * nf_stride * need * (1.0 + 2.0 / k), I_nf * (k + 2.0));
-            const double old_cost = std::min((double)push_volume_nf, (double)g->P) + (double)M + I_nf;
-            nfp = direct < old_cost;
-            if (trace)
-                std::fprintf(stderr, "[hgx bfs] level %d direct-pull rule: p %.4f need %.1f listed %.0f direct %.3g "
-                             "gather+pull %.3g -> %d\n", d, pbits, need, samp_nf * nf_stride, direct, old_cost, (int)nfp);
-        }
-        // dense level over a frontier whose rows fit the Infinity Cache: the frontier-code pull (bit 17)
-        const int4* fcrec = nullptr;
-        if (!nfp && !sparse && MODE == kSym && Lay<W>::G >= 4 && !ex && (lflags & kFc) &&
-            (double)front_atoms * W * 8.0 <= kFcFrontBytes)
-            fcrec = fc_records(g, s);
-        const bool fcp = fcrec != nullptr;
-        if (!opush) {   // the lists are reused as scratch; the sparse gather leaves candidate bits set
-            chained = false;
-            if (sparse) cand_clean = false;
-        }
-        if (fcp) {
-            if constexpr (Lay<W>::G >= 4 && MODE == kSym) {
-                const int64_t nwords = ceil_div(A, 64);
-                const int64_t cap = std::max<int64_t>((int64_t)front_atoms, 1);
-                const size_t fw_bytes = sizeof(u64x2) * (size_t)std::max<int64_t>(nwords, 1);
-                const size_t drow_bytes = sizeof(u64) * (size_t)kFcDenseCap * W;
-                u64x2* fwd = (u64x2*)g->alloc(fw_bytes);
-                u64* fcode = (u64*)g->alloc(sizeof(u64) * (size_t)cap);
-                u64* drow = (u64*)g->alloc(drow_bytes);
-                const hgx_graph* root = g->base ? g->base : g;
-                const int32_t n_hubs = root->fc_nhubs;
-                u64* hubtab = (u64*)g->alloc(sizeof(u64) * (size_t)std::max<int32_t>(n_hubs, 1));
-                u64* n_slots = ctr + (size_t)(max_levels_cap - 1) * kCtrBlock + 8;   // scratch slots
-                unsigned int* n_dense = (unsigned int*)(n_slots + 1);
-                Events e1 = tm.start(kKindFc, d);
-                HGX_HIP(hipMemsetAsync(n_slots, 0, 2 * sizeof(u64), s));
-                hgx_fc_slots<<<grid_for(nwords, 256, 2048), 256, 0, s>>>(nwords, fa, fwd, n_slots);
-                HGX_CHECK_LAUNCH();
-                hgx_fc_codes<W><<<grid_for(A, 256, 8192), 256, 0, s>>>(A, fwd, lvl, fcode, cap, drow, n_dense, c);
-                HGX_CHECK_LAUNCH();
-                if (n_hubs > 0) {
-                    hgx_fc_hubs<<<grid_for(n_hubs, 256, 64), 256, 0, s>>>(n_hubs, root->fc_hubs, fwd, fcode, hubtab);
-                    HGX_CHECK_LAUNCH();
-                }
-                hgx_fc_pull<W><<<grid_for(ceil_div(A, kFcTile) * 256, 256, 4096), 256, 0, s>>>(
-                    A, g->inc_off, fcrec, g->inc_type, want_type, fwd, fcode, drow, hubtab, n_hubs, lvl, vis, ever,
-                    full, lvl_next, fa_next, c, fm, lflags);
-                HGX_CHECK_LAUNCH();
-                tm.stop(e1);
-                if (g->n_chunks > 0) {
-                    Events e3 = tm.start(kKindFcHeavy, d);
-                    hgx_fc_pull_heavy<W><<<(unsigned)g->n_chunks, 256, 0, s>>>(g->chunks, fcrec, g->inc_type, want_type,
-                                                                             fwd, fcode, drow, hubtab, n_hubs, lvl,
-                                                                             vis, ever, full, hubacc, c, fm, lflags);
-                    HGX_CHECK_LAUNCH();
-                    tm.stop(e3);
-                    Events e4 = tm.start(kKindHub, d);
-                    hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis,
-                                                                   ever, full, lvl_next, fa_next, c, fm, nullptr);
-                    HGX_CHECK_LAUNCH();
-                    tm.stop(e4);
-                }
-                g->release(fwd, fw_bytes);   // stream-ordered reuse
-                g->release(fcode, sizeof(u64) * (size_t)cap);
-                g->release(drow, drow_bytes);
-                g->release(hubtab, sizeof(u64) * (size_t)std::max<int32_t>(n_hubs, 1));
-            }
-        } else if (nfp) {
-            if constexpr (Lay<W>::G >= 4 && MODE == kSym) {
-                Events e2 = tm.start(kKindNf, d);
-                HGX_HIP(hipMemsetAsync(fa_next, 0, bm_bytes, s));
-                u64* n_list = ctr + (size_t)(max_levels_cap - 1) * kCtrBlock + 8;   // scratch slot
-                u64* n_rlist = n_list + 1;                                          //   (the residual list's)
-                HGX_HIP(hipMemsetAsync(n_list, 0, 2 * sizeof(u64), s));
-                // the hint step: only where a co-target of any incident link is certainly a neighbour
-                const bool hinted = g->nf_hint == 1 && nf_opt != 0 && want_type < 0;
-                if (hinted && !g->nbr_hint) {   // once per snapshot
-                    HGX_HIP(hipMalloc(&g->nbr_hint, sizeof(int32_t) * (size_t)std::max<int64_t>(A, 1)));
-                    hgx_nbr_hint<<<grid_for(A * 8, 256, 8192), 256, 0, s>>>(A, g->inc_off, g->inc_row, g->tgt_off,
-                                                                           g->tgt_idx, g->nbr_hint);
-                    HGX_CHECK_LAUNCH();
-                    if (g->n_chunks > 0) {
-                        const size_t hk_bytes = sizeof(u64) * (size_t)g->n_heavy;
-                        u64* hkey = (u64*)g->alloc(hk_bytes);
-                        HGX_HIP(hipMemsetAsync(hkey, 0, hk_bytes, s));
-                        hgx_nbr_hint_heavy<<<(int)std::min<int64_t>(g->n_chunks, 8192), 256, 0, s>>>(
-                            g->chunks, g->n_chunks, g->inc_off, g->inc_row, g->tgt_off, g->tgt_idx, hkey);
-                        HGX_CHECK_LAUNCH();
-                        hgx_nbr_hint_heavy_out<<<grid_for(g->n_heavy, 256, 1024), 256, 0, s>>>(g->n_heavy, g->heavy_atom,
-                                                                                               hkey, g->nbr_hint);
-                        HGX_CHECK_LAUNCH();
-                        g->release(hkey, hk_bytes);   // stream-ordered reuse
-                    }
-                }
-                if (!g->hasinc) {   // once per snapshot
-                    HGX_HIP(hipMalloc(&g->hasinc, sizeof(u64) * (size_t)(ceil_div(A, 64) + 1)));
-                    hgx_hasinc<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(A, g->inc_off, (u64*)g->hasinc);
-                    HGX_CHECK_LAUNCH();
-                }
-                const u64* hasinc = (const u64*)g->hasinc;
-                hgx_nonfull_list<<<grid_for(ceil_div(A, 64), 256, 2048), 256, 0, s>>>(A, full, hasinc, clist, n_list);
-                HGX_CHECK_LAUNCH();
-                constexpr int nf_grid = 4096;
-                constexpr int G = Lay<W>::G;
-                // the cover test's step in entries (DESIGN 3.1 item 12 has the steps measured): with
-                // HGX_OPT_NF_PULL = 0 the group's G entries; else 2 where the rule (or value 2) chose the
-                // level, 1 on the late levels of the old rule; HGX_NF_E overrides (A/B builds)
-                const int nf_e = nf_opt == 0 ? G : ab_int("HGX_NF_E", nf_late ? 1 : 2);
-                const bool stepped = nf_e == 1 || nf_e == 2 || (nf_e == 4 && G > 4);   // hgx_nf_pull_e
-                // hubs: hgx_nf_pull_e leaves those not covered by their first kHeavyDegree entries to the
-                // chunk kernel and the hub finalise (whose blocks own the partial rows after the pull's)
-                const bool hubs = stepped && g->n_chunks > 0;
-                // The hint step's blocks own the partial rows after those.  Its grid: the workgroups the device
-                // holds at once (2048 ran a second, partly filled round: + 0.17 ms on config 2's level 2;
-                // HGX_NF_HINT_GRID: A/B builds), 256 at least -- a block then stores at most ceil(A / (256 *
-                // chunk)) * chunk rows, below 2^kFusePlanes for any int32 atom count, so the level is fused with
-                // the hint exactly when it is without.
-                static const int hint_resident = [&] {
-                    int per_cu = 0, cus = 0;
-                    HGX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hgx_nf_hint<W>, 256, 0));
-                    HGX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
-                    return std::min(std::max(per_cu * cus, 256), 4096);
-                }();
-                const int hint_grid = hinted ? std::max(ab_int("HGX_NF_HINT_GRID", hint_resident), 256) : 0;
-                if (fuse_ok && fuse_rows_ok(A, nf_grid, 256 / G) &&
-                    (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / G)) &&
-                    (!hinted || fuse_rows_ok(A, hint_grid, kNfHintChunk))) {
-                    lv_cblk = nf_grid + (hubs ? hub_grid : 0) + hint_grid;
-                    lv_cpart = (uint32_t*)g->alloc(cpart_size(lv_cblk));
-                }
-                const int32_t* nf_list = clist;
-                const u64* nf_n = n_list;
-                if (hinted) {   // the atoms their hint row covers are written here, the rest listed again
-                    hgx_nf_hint<W><<<hint_grid, 256, 0, s>>>(
-                        clist, n_list, g->nbr_hint, g->inc_off, fa, lvl, vis, ever, full, lvl_next, fa_next, c, fm,
-                        lv_cpart ? lv_cpart + (size_t)(lv_cblk - hint_grid) * W * 64 : nullptr, flist, n_rlist);
-                    HGX_CHECK_LAUNCH();
-                    nf_list = flist;
-                    nf_n = n_rlist;
-                }
-                u64* resid = nullptr;
-                if (hubs) {
-                    resid = (u64*)g->alloc(bm_bytes);
-                    HGX_HIP(hipMemsetAsync(resid, 0, bm_bytes, s));
-                }
-#define HGX_NF_ARGS nf_list, nf_n, g->inc_off, g->inc_row, g->inc_type, want_type, g->tgt_off, g->tgt_idx, fa, lvl, vis, \
-                    ever, full, lvl_next, fa_next, c, fm, lflags, lv_cpart
-                // (a test per entry with 8 atoms in flight spills: 4 entry slots there)
-                if (nf_e == 1) hgx_nf_pull_e<W, 1, 4><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
-                else if (nf_e == 2) hgx_nf_pull_e<W, 2, G><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
-                else if (stepped) hgx_nf_pull_e<W, G / 2, G><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS, resid);
-                else hgx_nf_pull<W><<<nf_grid, 256, 0, s>>>(HGX_NF_ARGS);
-#undef HGX_NF_ARGS
-                HGX_CHECK_LAUNCH();
-                if (hubs) {
-                    const int hgrid = (int)std::min<int64_t>(g->n_chunks, 2048);
-                    hgx_nf_pull_heavy<W><<<hgrid, 256, 0, s>>>(g->chunks, g->n_chunks, resid, g->inc_row, g->inc_type,
-                                                                want_type, g->tgt_off, g->tgt_idx, fa, lvl, vis, ever,
-                                                                hubacc, c, fm, lflags);
-                    HGX_CHECK_LAUNCH();
-                    hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(
-                        g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis, ever, full, lvl_next, fa_next, c, fm,
-                        lv_cpart ? lv_cpart + (size_t)nf_grid * W * 64 : nullptr);
-                    HGX_CHECK_LAUNCH();
-                    g->release(resid, bm_bytes);   // stream-ordered reuse
-                }
-                tm.stop(e2);
-            }
-        } else if (opush) {
-            // frontier-driven push (mark candidates, zero their rows, OR rows, finalise): the ordered
-            // modes always, the symmetric mode with HGX_OPT_BFS_FLAGS bit 5
-            const bool pre_work = !g->zacc_clean || g->zacc_bytes < row_bytes || (MODE != kSym && !g->inc_yf) ||
-                                  g->n_pchunks < 0 || !cand_clean || !chained;
-            if (pre_work) tm.break_chain();
-            if (!g->zacc_clean || g->zacc_bytes < row_bytes) {   // (re)establish the all-zero accumulator
-                if (g->zacc_bytes < row_bytes) {
-                    if (g->zacc) HGX_HIP(hipFree(g->zacc));
-                    g->zacc = nullptr;
-                    g->zacc_bytes = 0;
-                    HGX_HIP(hipMalloc(&g->zacc, row_bytes));
-                    g->zacc_bytes = row_bytes;
-                }
-                HGX_HIP(hipMemsetAsync(g->zacc, 0, g->zacc_bytes, s));
-            }
-            g->zacc_clean = false;   // until this level's finalise has run
-            u64* acc = (u64*)g->zacc;
-            if (MODE != kSym && !g->inc_yf) {   // once per snapshot
-                HGX_HIP(hipMalloc(&g->inc_yf, (size_t)g->I + 64));
-                hgx_inc_yield<<<grid_for(A * 64, 256, 8192), 256, 0, s>>>(A, g->inc_off, g->inc_row, g->tgt_off,
-                                                                       g->tgt_idx, g->inc_yf);
-                HGX_CHECK_LAUNCH();
-            }
-            const uint8_t* yf = g->inc_yf;
-            if (g->n_pchunks < 0) build_push_chunks(g);
-            // chained levels need no memset: the candidate words are zero-invariant, fa_next is cleared by
-            // hgx_opush and n_cl by the previous finalise
-            if (!cand_clean) HGX_HIP(hipMemsetAsync(cand, 0, bm_bytes, s));
-            if (!chained) {   // the frontier list from the bitmap (else the last finalise left it in fl)
-                if (!scratch_zero) {
-                    HGX_HIP(hipMemsetAsync(n_cl, 0, sizeof(u64), s));
-                    HGX_HIP(hipMemsetAsync(n_fl, 0, sizeof(u64), s));
-                }
-                const int fgrid = grid_for(ceil_div(A, 64), 256, 256);   // <= 256 list atomics per level
-                hgx_frontier_list<<<fgrid, 256, 0, s>>>(A, fa, g->inc_off, fl, n_fl, kPushLight);
-                HGX_CHECK_LAUNCH();
-            }
-            // 2048 waves grid-striding over the frontier list: config 5 levels of 20 to 35K atoms measured
-            // 19-113 us against 30-142 us with 8192 waves (the launch of mostly idle workgroups and
-            // the candidate-append contention) and 20-171 us with 1024 waves
-            static const int kPushGrid = [] {   // HGX_PUSH_GRID (A/B builds): override of the push grid (blocks)
-                const char* e = ab_env("HGX_PUSH_GRID");
-                const int v = e ? std::atoi(e) : 0;
-                return v >= 64 && v <= 8192 ? v : 512;
-            }();
-            const int lgrid = kPushGrid;
-            Events e2 = tm.start_chained(kKindPush, d);
-            // hub chunks inside hgx_opush while there are few of them (config 5: ~350 chunks, one launch
-            // less per level); a block per chunk in hgx_opush_heavy when there are many (config 2:
-            // ~380K chunks of 26K hubs: folded into 512 blocks the seed level took 0.58 ms against 0.41)
-            const bool fold = g->n_pchunks <= 8 * lgrid;
-            // hub chunks in the same launch when folded
-            hgx_opush<W, MODE><<<lgrid, 256, 0, s>>>(fl, n_fl, g->inc_off, g->inc_row, g->inc_type, want_type, yf,
-                                                         g->tgt_off, g->tgt_idx, lvl, full, cand, cl, n_cl, acc, c,
-                                                         fa_next, (int64_t)(bm_bytes / sizeof(u64)), g->pchunks,
-                                                         fold ? g->n_pchunks : 0, fa);
-            HGX_CHECK_LAUNCH();
-            if (!fold && g->n_pchunks > 0) {
-                hgx_opush_heavy<W, MODE><<<(unsigned)g->n_pchunks, 256, 0, s>>>(
-                    g->pchunks, fa, g->inc_row, g->inc_type, want_type, yf, g->tgt_off, g->tgt_idx, lvl, full, cand,
-                    cl, n_cl, acc, c);
-                HGX_CHECK_LAUNCH();
-            }
-            // finalise; re-zeroes the accumulator rows and candidate words it consumed and, without a
-            // ghost exchange, rewrites the candidate list into the next level's frontier list
-            // without an exchange the level's counters go straight to mapped host memory (no copy in the
-            // stream between this level and the next)
-            if (!ex) {
-                flag_level = true;
-                flag_seq = ++g->ctr_seq;
-                flag_slot = g->ctr_host + (size_t)(d & 1) * kHostSlot;
-                __atomic_store_n(flag_slot + cNum, (u64)0, __ATOMIC_RELEASE);
-            }
-            u64* lcount = nullptr;   // the new level's counts accumulated by the finalise (no exchange)
-            if (!ex && bt.pcnt && d + 1 < kDirectLevels) {
-                lcount = bt.pcnt + (size_t)(d + 1) * 1024;
-                bt.direct[d + 1] = 1;
-            }
-            hgx_push_finalize_list<W><<<512, 256, 0, s>>>(cl, n_cl, g->inc_off, acc, cand, vis, ever, full,
-                                                           lvl_next, fa_next, c, fm, ex ? 0 : 1, ex ? nullptr : n_fl,
-                                                           ticket, flag_level ? flag_slot : nullptr, flag_seq, lcount);
-            HGX_CHECK_LAUNCH();
-            g->zacc_clean = true;   // every accumulated row is in the candidate list and re-zeroed
-            cand_clean = true;
-            chained = !ex;
-            std::swap(fl, cl);
-            std::swap(n_fl, n_cl);
-            tm.stop_chained(e2);
-        } else {
-        if (sparse) {
-            Events e0 = tm.start(kKindGather, d);
-            HGX_HIP(hipMemsetAsync(lcand, 0, la_bytes, s));
-            HGX_HIP(hipMemsetAsync(cand, 0, bm_bytes, s));
-            hgx_frontier_links<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(
-                A, fa, g->inc_off, g->inc_row, g->link_type, want_type, lcand);
-            HGX_CHECK_LAUNCH();
-            if (g->n_chunks > 0) {
-                hgx_frontier_links_heavy<<<(unsigned)g->n_chunks, 256, 0, s>>>(g->chunks, fa, g->inc_row,
-                                                                             g->link_type, want_type, lcand);
-                HGX_CHECK_LAUNCH();
-            }
-            tm.stop(e0);
-        }
-        u64* lc = sparse ? lcand : nullptr;
-        u64* cd = sparse ? cand : nullptr;
-
-        const bool v2 = Lay<W>::G >= 4 && !sparse && !(lflags & 64);   // MLP-restructured dense kernels
-        // A frontier whose incidence volume covers the links twice leaves few links inactive: the
-        // gather then writes a (zero) row for every link and the pull reads rows without probing la
-        // -- one dependent load fewer per incidence chunk (HGX_OPT_BFS_FLAGS bit 7).
-        if (v2 && (lflags & 128) && MODE == kSym && push_volume_nf >= 2 * (u64)M) lflags |= kAllRows;
-        // hub mask: an all-rows level of the MLP kernels; C, fr and the rule's counters first (the frontier is final)
-        bool hmask = false;
-        u64* hm_slot = nullptr;
-        u64 hm_limit = 0;
-        int hm_S = 0;
-        if constexpr (MODE == kSym && Lay<W>::G >= 4) {
-            // (hgx_hub_mask reads every frontier row: under the rule only while the frontier is at most half of the atoms)
-            hmask = hm_ok && v2 && (lflags & kAllRows) && !(lflags & (kGatherO5 | kHeavyMlp2)) &&
-                    (g->hub_mask == 2 || front_atoms * 2 <= (u64)A);
-            if (hmask) {
-                hub_top_list(g, s);   // once per snapshot
-                hm_slot = hm + (size_t)(hm_levels & 1) * kHmSlot;
-                hm_limit = (u64)(g->I_heavy / 4);
-                hm_S = (int)bt.S;
-                Events e0 = tm.start(kKindGather, d);
-                hgx_hub_mask<W><<<grid_for(ceil_div(A, 64), 256, 2048), 256, 0, s>>>(
-                    A, g->top_list, std::min(g->hub_mask_t, g->top_n), fa, lvl, g->inc_off, hm + 2 * kHmSlot, hm_fr,
-                    hm_slot, hm + (size_t)((hm_levels + 1) & 1) * kHmSlot);
-                HGX_CHECK_LAUNCH();
-                tm.stop(e0);
-                ++hm_levels;
-                if (trace) {   // the rule's inputs (a host wait: tracing only)
-                    u64 h[kHmSlot + 16];
-                    HGX_HIP(hipMemcpyAsync(h, hm_slot, sizeof(u64) * kHmSlot, hipMemcpyDeviceToHost, s));
-                    HGX_HIP(hipMemcpyAsync(h + kHmSlot, hm + 2 * kHmSlot, sizeof(u64) * 16, hipMemcpyDeviceToHost, s));
-                    HGX_HIP(hipStreamSynchronize(s));
-                    u64 fdeg = 0, pc = 0;
-                    for (int k = 0; k < kStatShards; ++k) fdeg += h[k * kStatStride + kHmDeg];
-                    for (int w = 0; w < W; ++w) pc += (u64)__builtin_popcountll(h[kHmSlot + w]);
-                    std::fprintf(stderr, "[hgx bfs] level %d hub mask: T %d listed on the frontier %llu |C| %llu (row %llu) "
-                                 "fr degree sum %llu limit %llu\n", d, std::min(g->hub_mask_t, g->top_n),
-                                 (unsigned long long)h[kHmListed], (unsigned long long)h[kHmPop], (unsigned long long)pc,
-                                 (unsigned long long)fdeg, (unsigned long long)hm_limit);
-                }
-            }
-        }
-        Events e1 = tm.start(kKindGather, d);
-        if constexpr (MODE == kSym && Lay<W>::G >= 4) {
-            if (hmask)
-                hgx_link_gather2_fr<W><<<gather_grid, block, 0, s>>>(
-                    M, g->tgt_off, g->tgt_idx, g->link_type, want_type, fa, full, lvl, lf, la, c, fm, lflags, hm_fr,
-                    hm_lr, hm_slot, g->hub_mask, hm_S, hm_limit);
-        }
-        if constexpr (Lay<W>::G >= 4) {
-            if (v2 && !hmask)
-            {
-                if (lflags & kGatherO5)   // diagnostic A/B (bit 10)
-                    hgx_link_gather2_o5<W, MODE == kSym><<<gather_grid, block, 0, s>>>(
-                        M, g->tgt_off, g->tgt_idx, g->link_type, want_type, fa, full, lvl, lf, la, c, fm, lflags);
-                else
-                    hgx_link_gather2<W, MODE == kSym><<<gather_grid, block, 0, s>>>(
-                        M, g->tgt_off, g->tgt_idx, g->link_type, want_type, fa, full, lvl, lf, la, c, fm, lflags);
-            }
-        }
-        if (!v2)
-            hgx_link_gather<W, MODE == kSym><<<gather_grid, block, 0, s>>>(M, g->tgt_off, g->tgt_idx, g->link_type,
-                                                                          want_type, fa, full, lvl, lf, la, c, fm,
-                                                                          lflags, lc, cd);
-        HGX_CHECK_LAUNCH();
-        tm.stop(e1);
-        if (sparse && MODE == kSym) {
-            // push direction: candidates are few, hubs must not be re-scanned
-            Events e2 = tm.start(kKindPull, d);
-            hgx_push_zero<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(A, W, cand, full, lvl_next);
-            HGX_CHECK_LAUNCH();
-            hgx_push_rows<<<grid_for(ceil_div(M, 64) * 64, 256, 4096), 256, 0, s>>>(M, W, la, g->tgt_off, g->tgt_idx,
-                                                                                 lf, full, lvl_next);
-            HGX_CHECK_LAUNCH();
-            hgx_push_finalize<W><<<pull_grid, block, 0, s>>>(A, g->inc_off, cand, vis, ever, full, lvl_next, fa_next,
-                                                             c, fm);
-            HGX_CHECK_LAUNCH();
-            tm.stop(e2);
-        } else {
-        Events e2 = tm.start(kKindPull, d);
-        if constexpr (Lay<W>::G >= 4 && MODE == kSym) {
-            if (v2)
-            {
-                // two atoms of a group interleaved (152 VGPRs, 3 waves/SIMD): config 2 pull 5.73 -> 5.23 ms
-                // a step against four (184 VGPRs, 2 waves/SIMD, dropped in r02); a tile's atoms placed in
-                // descending degree order (5.20 -> 5.13 ms, profiles/r02r_ab_pull_sort.log).  Bit 11 (A/B):
-                // half of a group's rows in flight at once (fewer VGPRs, more waves per SIMD).
-                // fused counts: the pull's blocks own the first pull_grid partial rows of the level, the hub
-                // finalise's blocks (when the snapshot has hubs) the hub_grid rows after them
-                const bool hubs = g->n_chunks > 0;
-                if (fuse_ok && fuse_rows_ok(ceil_div(A, 64) * 64, pull_grid, block) &&
-                    (!hubs || fuse_rows_ok(g->n_heavy, hub_grid, block / Lay<W>::G))) {
-                    lv_cblk = pull_grid + (hubs ? hub_grid : 0);
-                    lv_cpart = (uint32_t*)g->alloc(cpart_size(lv_cblk));
-                }
-                if (lflags & 2048)
-                    hgx_atom_pull2<W, 2, true, Lay<W>::G / 2><<<pull_grid, block, 0, s>>>(
-                        A, g->inc_off, g->inc_row, la, lf, vis, ever, full, lvl_next, fa_next, c, fm, lflags, own_bm,
-                        lv_cpart);
-                else
-                    hgx_atom_pull2<W, 2, true, Lay<W>::G><<<pull_grid, block, 0, s>>>(
-                        A, g->inc_off, g->inc_row, la, lf, vis, ever, full, lvl_next, fa_next, c, fm, lflags, own_bm,
-                        lv_cpart);
-            }
-        }
-        if (!(v2 && MODE == kSym))
-            hgx_atom_pull<W, MODE><<<pull_grid, block, 0, s>>>(A, g->inc_off, g->inc_row, la, lf, g->tgt_off,
-                                                               g->tgt_idx, fa, lvl, vis, ever, full, lvl_next,
-                                                               fa_next, c, fm, lflags, cd);
-        HGX_CHECK_LAUNCH();
-        tm.stop(e2);
-        if (g->n_chunks > 0) {
-            Events e3 = tm.start(kKindHeavy, d);
-            if constexpr (MODE == kSym && Lay<W>::G >= 4) {
-                if (hmask)
-                    hgx_atom_pull_hub<W><<<(unsigned)g->n_chunks, block, 0, s>>>(
-                        g->chunks, g->inc_row, la, lf, hm_lr, hm + 2 * kHmSlot, hm_slot, vis, ever, full, hubacc, c, fm,
-                        lflags, g->hub_mask, hm_S, hm_limit, g->hub_mask_sched);
-            }
-            if (!hmask)
-            hgx_atom_pull_heavy<W, MODE><<<(unsigned)g->n_chunks, block, 0, s>>>(
-                    g->chunks, g->inc_row, la, lf, g->tgt_off, g->tgt_idx, fa, lvl, vis, ever, full, hubacc, c, fm,
-                    lflags, cd);
-            HGX_CHECK_LAUNCH();
-            tm.stop(e3);
-            Events e4 = tm.start(kKindHub, d);
-            hgx_hub_finalize<W><<<hub_grid, block, 0, s>>>(
-                g->n_heavy, g->heavy_atom, g->inc_off, hubacc, vis, ever, full, lvl_next, fa_next, c, fm,
-                lv_cpart ? lv_cpart + (size_t)pull_grid * W * 64 : nullptr);
-            HGX_CHECK_LAUNCH();
-            tm.stop(e4);
-        }
-        }
-        }   // not an ordered push level
-        u64 new_global = 0, part_push = 0;
-        if (ex) {
-            double lb = 0, pm = 0;
-            new_global = ex->template level<W>(lvl_next, fa_next, vis, ever, full, fm, &part_push, &lb, &pm, tm, d,
-                                               d + 1 >= maxd);
-            if (d < 64) {
-                res->stats.level_xbytes[d] += lb;
-                res->stats.level_xpair_max[d] = std::max(res->stats.level_xpair_max[d], pm);
-                res->stats.level_xtrips[d] = std::max(res->stats.level_xtrips[d], (int32_t)ex->trips);
-            }
-        }
-        Pend& pn = pend[d & 1];
-        pn.d = d;
-        pn.lvl_next = lvl_next;
-        pn.fa_next = fa_next;
-        pn.kind = fcp ? 4 : nfp ? 3 : sparse ? (opush ? 2 : 1) : 0;
-        pn.allrows = (lflags & kAllRows) ? 1 : 0;
-        pn.new_global = new_global;
-        pn.part_push = part_push;
-        pn.flag = flag_level;
-        pn.seq = flag_seq;
-        pn.slot = flag_slot;
-        pn.cpart = lv_cpart;
-        pn.cblk = lv_cblk;
-        // a dense level's sample for the next level's direct-pull rule
-        pn.sampled = !flag_level && !sparse && nf_eligible && nf_opt == 1 && d + 1 < maxd;
-        if (pn.sampled) {
-            hgx_level_sample<W><<<grid_for(ceil_div(A, nf_stride), 256, 4096), 256, 0, s>>>(
-                A, nf_stride, fa_next, lvl_next, full, g->inc_off, c);
-            HGX_CHECK_LAUNCH();
-        }
-        if (!flag_level) {
-            tm.break_chain();
-            HGX_HIP(hipMemcpyAsync(pn.h, c, sizeof(u64) * kCtrBlock, hipMemcpyDeviceToHost, s));
-            HGX_HIP(hipEventRecord(pn.ev, s));
-        }
-        ++npend;
-        cur_lvl = lvl_next;
-        cur_fa = fa_next;
-        // Pipelined push levels: while this level runs, the next one is issued as a push level when this
-        // level ran on a frontier below the sparse limit (a push is exact on any frontier, so a wrong
-        // guess only costs speed); an empty frontier costs it three near-empty launches, so the
-        // counters are read one level late.
+    // Reads the levels in flight..  Pipelined push levels: while this level runs, the next one is issued as a push level
+    // when this level ran on a frontier below the sparse limit (a push is exact on any frontier, so a wrong guess only
+    // costs speed); an empty frontier costs it three near-empty launches, so the counters are read one level late.
+    void drain(int32_t d, bool opush) {
         for (;;) {
             const bool can_spec = pipe_ok && npend == 1 && opush && push_volume < sparse_limit && d + 1 < maxd;
             if (npend == 0 || can_spec) break;
@@ -5558,56 +5565,58 @@ void run_levels(hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_dep
                 for (; npend > 0; --npend) {   // a level issued after the last frontier: its rows are empty
                     Pend& q = pend[(d - npend + 1) & 1];
                     if (q.flag) spin_sync(s);
-                    else wait_event(q.ev);
-                    g->release(q.lvl_next, row_bytes);
-                    g->release(q.fa_next, bm_bytes);
-                    if (q.cpart) g->release(q.cpart, cpart_size(q.cblk));
+                    else spin_event(q.ev);
+                    drop_rows(q);
                 }
                 break;
             }
         }
     }
-    if (ex) {
-        res->stats.bytes_exchanged += ex->bytes_sent;
-        res->stats.xwords_nonzero += ex->nz_words;
-        res->stats.xwords_total += ex->words;
+
+    void run() {
+        for (int32_t d = 0; d < maxd && !stop; ++d) {
+            Pend& pn = begin_level(d);
+            const LevelPlan pl = plan(d);
+            pn.kind = pl.kind;
+            pn.allrows = (pl.lflags & kAllRows) ? 1 : 0;
+            if (pl.kind != kLvPush) {   // the lists are reused as scratch; the sparse gather leaves candidate bits set
+                chained = false;
+                if (pl.kind == kLvSparseGather) cand_clean = false;
+            }
+            switch (pl.kind) {
+                case kLvFcPull: if constexpr (MODE == kSym && Lay<W>::G >= 4) issue_fc_pull(pl, pn); break;
+                case kLvDirectPull: if constexpr (MODE == kSym && Lay<W>::G >= 4) issue_direct_pull(pl, pn); break;
+                case kLvPush: issue_push(pn); break;
+                case kLvSparseGather: issue_sparse_gather(pl, pn); break;
+                case kLvDense: issue_dense(pl, pn); break;
+            }
+            close_level(pn);
+            drain(d, pl.kind == kLvPush);
+        }
+        if (ex) {
+            res->stats.bytes_exchanged += ex->bytes_sent;
+            res->stats.xwords_nonzero += ex->nz_words;
+            res->stats.xwords_total += ex->words;
+        }
+        // levels left to a counting pass (level 0 of a whole-graph batch is {seed}: no pass, see ensure_counts)
+        for (size_t lev = (bt.pcnt && !g->shard) ? 1 : 0; lev < bt.lvl.size(); ++lev) {
+            const bool dir = lev < bt.direct.size() && bt.direct[lev];
+            const bool fused = !eager && lev < bt.cpart.size() && bt.cpart[lev];
+            if (!dir && !fused) ++bt.pass_levels;
+        }
     }
-    // levels left to a counting pass (level 0 of a whole-graph batch is {seed}: no pass, see ensure_counts)
-    for (size_t lev = (bt.pcnt && !g->shard) ? 1 : 0; lev < bt.lvl.size(); ++lev) {
-        const bool dir = lev < bt.direct.size() && bt.direct[lev];
-        const bool fused = !eager && lev < bt.cpart.size() && bt.cpart[lev];
-        if (!dir && !fused) ++bt.pass_levels;
-    }
-    g->release(vis, row_bytes);
-    if (lf) g->release(lf, sizeof(u64) * (size_t)std::max<int64_t>(M, 1) * W);
-    g->release(hubacc, sizeof(u64) * (size_t)std::max<int64_t>(g->n_heavy, 1) * W);
-    g->release(ever, bm_bytes);
-    g->release(full, bm_bytes);
-    g->release(la, la_bytes);
-    if (hm) {
-        g->release(hm, hm_bytes);
-        g->release(hm_fr, 2 * bm_bytes);
-        g->release(hm_lr, la_bytes);
-    }
-    if (lcand) g->release(lcand, la_bytes);
-    if (cand) g->release(cand, bm_bytes);
-    if (flist) g->release(flist, flist_bytes);
-    if (clist) g->release(clist, flist_bytes);
-    g->release(ctr, sizeof(u64) * kCtrBlock * max_levels_cap);
-    g->release(d_atoms, sizeof(int32_t) * seed_atoms.size());
-    g->release(d_rows, sizeof(u64) * seed_rows.size());
-}
+};
 
 template <int W>
 void run_mode(int mode, hgx_graph* g, hgx_bfs_result* res, BfsBatch& bt, int32_t max_depth, int32_t want_type,
-              const std::vector<int32_t>& sa, const std::vector<u64>& sr, Timer& tm,
-              std::vector<std::vector<u64>>& lc, Transport* tr) {
+              const std::vector<int32_t>& sa, const std::vector<u64>& sr, Timer& tm, std::vector<LevelRec>& lc,
+              Transport* tr) {
     switch (mode) {
-        case kSym: run_levels<W, kSym>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr); break;
-        case kAfterFirst: run_levels<W, kAfterFirst>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr); break;
-        case kBeforeFirst: run_levels<W, kBeforeFirst>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr); break;
-        case kBeforeLast: run_levels<W, kBeforeLast>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr); break;
-        default: run_levels<W, kAfterLast>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr); break;
+        case kSym: LevelLoop<W, kSym>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr).run(); break;
+        case kAfterFirst: LevelLoop<W, kAfterFirst>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr).run(); break;
+        case kBeforeFirst: LevelLoop<W, kBeforeFirst>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr).run(); break;
+        case kBeforeLast: LevelLoop<W, kBeforeLast>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr).run(); break;
+        default: LevelLoop<W, kAfterLast>(g, res, bt, max_depth, want_type, sa, sr, tm, lc, tr).run(); break;
     }
 }
 
@@ -5922,6 +5931,106 @@ void hgx::pbfs_run(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n_
 
 namespace {
 
+// Level d of bt (a frontier of n_front atoms) into r's statistics: launches, rows, algorithmic bytes.
+void account_level(hgx_bfs_result* r, const BfsBatch& bt, int mode, int d, const LevelRec& rec, double n_front) {
+    const hgx_graph* g = r->g;
+    const u64* c = rec.c;
+    const int64_t A = g->A, M = g->M, P = g->P, I = g->I;
+    const double rowb = 8.0 * bt.W;
+    const bool typed = r->typed;
+    const double I_light = (double)(I - g->I_heavy), I_heavy = (double)g->I_heavy;
+    // hgx_link_gather: tgt_off + tgt_idx (+ link_type) + frontier/full bitmaps + gathered rows
+    //                  + lf writes + la words
+    const bool fc_level = rec.kind == kLvFcPull;   // (its hub chunks ran)
+    const bool sparse_level = rec.kind != kLvDense && !fc_level;
+    const double scan_links = sparse_level ? (double)c[cActiveLinks] : (double)M;
+    const double scan_pins = sparse_level ? (double)c[cActivePins] : (double)P;
+    double b_gather = 8.0 * (scan_links + 1) + 4.0 * scan_pins + (typed ? 4.0 * scan_links : 0.0) +
+                            A / 4.0 + rowb * c[cActivePins] +
+                            (mode == kSym ? rowb * c[cActiveLinks] : 0.0) + M / 8.0;
+    // hgx_atom_pull: inc_off + light inc_row + la bitmap + pulled rows + vis reads + lvl/vis writes
+    //                + ever/full/fa_next words (sparse levels: candidate words + pushed rows)
+    double b_pull = (sparse_level ? 8.0 * (A / 64.0) : 8.0 * (A + 1) + 4.0 * I_light) + M / 8.0 +
+                          rowb * c[cIncLight] + rowb * c[cVisLight] + 2.0 * rowb * c[cNewLight] +
+                          3.0 * A / 8.0;
+    int pull_kind = HGX_K_ATOM_PULL;
+    switch (rec.kind) {
+        case kLvDirectPull:   // non-full pull: no gather
+            pull_kind = HGX_K_NF_PULL;
+            b_gather = 0.0;
+            // full bitmap + inc_off of the listed atoms + list write/read + entries (inc_row, inc_type,
+            // tgt_off pair) + pins + frontier bitmap + frontier rows + vis reads + lvl/vis writes + bitmaps
+            b_pull = A / 8.0 + 24.0 * c[cCand] + 4.0 * A / 64.0 + (8.0 + (typed ? 4.0 : 0.0) + 16.0) * c[cIncLight] +
+                     4.0 * c[cActivePins] + A / 8.0 + rowb * c[cNfRows] + rowb * c[cVisLight] +
+                     2.0 * rowb * c[cNewLight] + 3.0 * A / 8.0;
+            // the hint step (cNfRows / cVisLight / cNewLight above hold its hint, vis and written rows): the
+            // hint entry of every listed atom, the residual list written and read
+            if ((double)rec.hinted > 0) {
+                b_pull += 4.0 * c[cCand] + 8.0 * ((double)c[cCand] - (double)rec.hinted);
+                r->stats.nf_hint_atoms += (int64_t)rec.hinted;
+            }
+            break;
+        case kLvFcPull: {   // frontier-code pull: no gather, no lf
+            pull_kind = HGX_K_FC_PULL;
+            b_gather = 0.0;
+            // codes: frontier bitmap (twice) + prefixes + the frontier atoms' rows + their codes;
+            // pull: inc_off + full bitmap + light records (+ inc_type) + frontier words / prefixes / codes of
+            // the frontier targets + dense frontier rows + vis reads + lvl/vis writes + bitmap words
+            const double e_light = (double)c[cIncLight], e_all = e_light + (double)c[cIncHeavy];
+            b_pull = 2.0 * A / 8.0 + 4.0 * A / 64.0 + n_front * (rowb + 8.0) +
+                     8.0 * (A + 1) + A / 8.0 + e_light * (32.0 + (typed ? 4.0 : 0.0)) +
+                     (8.0 + 4.0 + 8.0) * c[cActivePins] * e_light / std::max(e_all, 1.0) +
+                     rowb * c[cNfRows] * e_light / std::max(e_all, 1.0) + rowb * c[cVisLight] +
+                     2.0 * rowb * c[cNewLight] + 3.0 * A / 8.0;
+            break;
+        }
+        case kLvPush:   // frontier push: no gather; two frontier passes + finalise
+            pull_kind = HGX_K_FRONTIER_PUSH;
+            b_gather = 0.0;
+            // frontier scan + scanned entries (inc_type + yield flag) + links (inc_row, tgt_off pair) + pins
+            // + one word RMW per pair + candidates (acc read + re-zero) + vis reads + lvl/vis writes
+            // + cleared bitmaps
+            b_pull = 8.0 * (A / 64.0) + 5.0 * c[cScanned] + 20.0 * c[cActiveLinks] + 4.0 * c[cActivePins] +
+                     16.0 * c[cIncLight] +
+                     2.0 * rowb * c[cCand] + rowb * c[cVisLight] + 2.0 * rowb * c[cNewLight] + 2.0 * A / 8.0;
+            break;
+        default:   // kLvDense, kLvSparseGather: gather + pull as above
+            break;
+    }
+    r->stats.bytes_kernel[HGX_K_LINK_GATHER] += b_gather;
+    r->stats.bytes_kernel[pull_kind] += b_pull;
+    double b_heavy = 0, b_hub = 0;
+    if (g->n_chunks > 0 && !sparse_level) {
+        if (fc_level) {   // chunk table + the streamed records of the chunks that ran + code lookups
+            const double e_all = (double)c[cIncLight] + (double)c[cIncHeavy];
+            const double share = (double)c[cIncHeavy] / std::max(e_all, 1.0);
+            b_heavy = 24.0 * g->n_chunks + rowb * g->n_chunks +
+                      c[cIncHeavy] * (32.0 + (typed ? 4.0 : 0.0)) + 20.0 * c[cActivePins] * share +
+                      rowb * c[cNfRows] * share + rowb * g->n_chunks;
+        } else {
+            b_heavy = 24.0 * g->n_chunks + 4.0 * I_heavy + rowb * c[cIncHeavy] + rowb * g->n_chunks;
+        }
+        b_hub = 4.0 * g->n_heavy + 2.0 * rowb * g->n_heavy + rowb * c[cAccHub] + 2.0 * rowb * c[cNewHub];
+        const int heavy_kind = fc_level ? HGX_K_FC_HEAVY : HGX_K_PULL_HEAVY;
+        r->stats.bytes_kernel[heavy_kind] += b_heavy;
+        r->stats.bytes_kernel[HGX_K_HUB_FINALIZE] += b_hub;
+        r->stats.launches[heavy_kind] += 1;
+        r->stats.launches[HGX_K_HUB_FINALIZE] += 1;
+    }
+    if (rec.kind == kLvDense) {   // dense gather + pull: the hub-mask pull's two counters
+        r->stats.hub_mask_entries += (int64_t)c[cCand];
+        r->stats.hub_mask_skipped += (int64_t)c[cNfRows];
+    }
+    if (d < 64) {
+        for (int k = 0; k < 8; ++k) r->stats.level_rows[d][k] += (int64_t)c[k];
+        r->stats.level_bytes[d] += b_gather + b_pull + b_heavy + b_hub;
+        r->stats.level_sparse[d] = (int32_t)rec.kind;
+    }
+    if (rec.kind == kLvDense || rec.kind == kLvSparseGather) r->stats.launches[HGX_K_LINK_GATHER] += 1;
+    r->stats.launches[pull_kind] += 1;
+    if (d < 64) r->stats.level_new[d] += (int64_t)c[cNewAtoms];
+}
+
 void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
                     const hgx_algen_opts* opts, hgx_bfs_result** out) {
     hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
@@ -5956,7 +6065,7 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
 
     Timer tm(g);
     if (tm.on) HGX_HIP(hipEventRecord(tm.all.a, g->stream));
-    std::vector<std::vector<u64>> level_ctr;
+    std::vector<LevelRec> level_ctr;
     int max_expanded = 0;
     // Whole-graph batches: every seed first runs in one workgroup (hgx_bfs_block); the rows engine
     // below takes the seeds that outgrew it, compacted.
@@ -5984,7 +6093,8 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
         n_seeds = (int32_t)rseeds.size();
     }
     for (int32_t s0 = 0; s0 < n_seeds; s0 += 1024) {
-        BfsBatch bt;
+        r->batches.emplace_back();   // in the result from the start: the guard owns its rows on an error path
+        BfsBatch& bt = r->batches.back();
         bt.seed0 = s0;
         bt.S = std::min<int32_t>(1024, n_seeds - s0);
         bt.W = words_for(bt.S);
@@ -6023,103 +6133,13 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
             case 8: run_mode<8>(mode, g, r, bt, max_depth, o.link_type, sa, sr, tm, level_ctr, tr); break;
             default: run_mode<16>(mode, g, r, bt, max_depth, o.link_type, sa, sr, tm, level_ctr, tr); break;
         }
-        // algorithmic bytes of every launch of this batch
-        const int64_t A = g->A, M = g->M, P = g->P, I = g->I;
-        const double rowb = 8.0 * bt.W;
-        const bool typed = o.link_type >= 0;
         const int nexp = (int)(level_ctr.size() - before);
         bt.n_expanded = nexp;
         max_expanded = std::max(max_expanded, nexp);
-        const double I_light = (double)(I - g->I_heavy), I_heavy = (double)g->I_heavy;
-        for (int d = 0; d < nexp; ++d) {
-            const auto& c = level_ctr[before + d];
-            // hgx_link_gather: tgt_off + tgt_idx (+ link_type) + frontier/full bitmaps + gathered rows
-            //                  + lf writes + la words
-            const bool fc_level = c[cDirRows] == 4;   // frontier-code pull (its hub chunks ran)
-            const bool sparse_level = c[cDirRows] != 0 && !fc_level;
-            const double scan_links = sparse_level ? (double)c[cActiveLinks] : (double)M;
-            const double scan_pins = sparse_level ? (double)c[cActivePins] : (double)P;
-            double b_gather = 8.0 * (scan_links + 1) + 4.0 * scan_pins + (typed ? 4.0 * scan_links : 0.0) +
-                                    A / 4.0 + rowb * c[cActivePins] +
-                                    (mode == kSym ? rowb * c[cActiveLinks] : 0.0) + M / 8.0;
-            // hgx_atom_pull: inc_off + light inc_row + la bitmap + pulled rows + vis reads + lvl/vis writes
-            //                + ever/full/fa_next words (sparse levels: candidate words + pushed rows)
-            double b_pull = (sparse_level ? 8.0 * (A / 64.0) : 8.0 * (A + 1) + 4.0 * I_light) + M / 8.0 +
-                                  rowb * c[cIncLight] + rowb * c[cVisLight] + 2.0 * rowb * c[cNewLight] +
-                                  3.0 * A / 8.0;
-            const bool opush_level = c[cDirRows] == 2 || c[cDirRows] == 3;
-            if (c[cDirRows] == 3) {   // non-full pull: no gather
-                b_gather = 0.0;
-                // full bitmap + inc_off of the listed atoms + list write/read + entries (inc_row, inc_type,
-                // tgt_off pair) + pins + frontier bitmap + frontier rows + vis reads + lvl/vis writes + bitmaps
-                b_pull = A / 8.0 + 24.0 * c[cCand] + 4.0 * A / 64.0 + (8.0 + (typed ? 4.0 : 0.0) + 16.0) * c[cIncLight] +
-                         4.0 * c[cActivePins] + A / 8.0 + rowb * c[cNfRows] + rowb * c[cVisLight] +
-                         2.0 * rowb * c[cNewLight] + 3.0 * A / 8.0;
-                // the hint step (cNfRows / cVisLight / cNewLight above hold its hint, vis and written rows): the
-                // hint entry of every listed atom, the residual list written and read
-                const double hinted = c.size() > (size_t)cNum ? (double)c[cNum] : 0.0;
-                if (hinted > 0) {
-                    b_pull += 4.0 * c[cCand] + 8.0 * ((double)c[cCand] - hinted);
-                    r->stats.nf_hint_atoms += (int64_t)c[cNum];
-                }
-            } else if (fc_level) {   // frontier-code pull: no gather, no lf
-                b_gather = 0.0;
-                // codes: frontier bitmap (twice) + prefixes + the frontier atoms' rows + their codes;
-                // pull: inc_off + full bitmap + light records (+ inc_type) + frontier words / prefixes / codes of
-                // the frontier targets + dense frontier rows + vis reads + lvl/vis writes + bitmap words
-                const double n_front = (double)(d == 0 ? bt.S : level_ctr[before + d - 1][cNewAtoms]);
-                const double e_light = (double)c[cIncLight], e_all = e_light + (double)c[cIncHeavy];
-                b_pull = 2.0 * A / 8.0 + 4.0 * A / 64.0 + n_front * (rowb + 8.0) +
-                         8.0 * (A + 1) + A / 8.0 + e_light * (32.0 + (typed ? 4.0 : 0.0)) +
-                         (8.0 + 4.0 + 8.0) * c[cActivePins] * e_light / std::max(e_all, 1.0) +
-                         rowb * c[cNfRows] * e_light / std::max(e_all, 1.0) + rowb * c[cVisLight] +
-                         2.0 * rowb * c[cNewLight] + 3.0 * A / 8.0;
-            } else if (opush_level) {   // frontier push: no gather; two frontier passes + finalise
-                b_gather = 0.0;
-                // frontier scan + scanned entries (inc_type + yield flag) + links (inc_row, tgt_off pair) + pins
-                // + one word RMW per pair + candidates (acc read + re-zero) + vis reads + lvl/vis writes
-                // + cleared bitmaps
-                b_pull = 8.0 * (A / 64.0) + 5.0 * c[cScanned] + 20.0 * c[cActiveLinks] + 4.0 * c[cActivePins] +
-                         16.0 * c[cIncLight] +
-                         2.0 * rowb * c[cCand] + rowb * c[cVisLight] + 2.0 * rowb * c[cNewLight] + 2.0 * A / 8.0;
-            }
-            const int pull_kind = fc_level ? HGX_K_FC_PULL : c[cDirRows] == 3 ? HGX_K_NF_PULL
-                                  : c[cDirRows] == 2 ? HGX_K_FRONTIER_PUSH : HGX_K_ATOM_PULL;
-            r->stats.bytes_kernel[HGX_K_LINK_GATHER] += b_gather;
-            r->stats.bytes_kernel[pull_kind] += b_pull;
-            double b_heavy = 0, b_hub = 0;
-            if (g->n_chunks > 0 && !sparse_level) {
-                if (fc_level) {   // chunk table + the streamed records of the chunks that ran + code lookups
-                    const double e_all = (double)c[cIncLight] + (double)c[cIncHeavy];
-                    const double share = (double)c[cIncHeavy] / std::max(e_all, 1.0);
-                    b_heavy = 24.0 * g->n_chunks + rowb * g->n_chunks +
-                              c[cIncHeavy] * (32.0 + (typed ? 4.0 : 0.0)) + 20.0 * c[cActivePins] * share +
-                              rowb * c[cNfRows] * share + rowb * g->n_chunks;
-                } else {
-                    b_heavy = 24.0 * g->n_chunks + 4.0 * I_heavy + rowb * c[cIncHeavy] + rowb * g->n_chunks;
-                }
-                b_hub = 4.0 * g->n_heavy + 2.0 * rowb * g->n_heavy + rowb * c[cAccHub] + 2.0 * rowb * c[cNewHub];
-                const int heavy_kind = fc_level ? HGX_K_FC_HEAVY : HGX_K_PULL_HEAVY;
-                r->stats.bytes_kernel[heavy_kind] += b_heavy;
-                r->stats.bytes_kernel[HGX_K_HUB_FINALIZE] += b_hub;
-                r->stats.launches[heavy_kind] += 1;
-                r->stats.launches[HGX_K_HUB_FINALIZE] += 1;
-            }
-            if (c[cDirRows] == 0) {   // dense gather + pull: the hub-mask pull's two counters
-                r->stats.hub_mask_entries += (int64_t)c[cCand];
-                r->stats.hub_mask_skipped += (int64_t)c[cNfRows];
-            }
-            if (d < 64) {
-                for (int k = 0; k < 8; ++k) r->stats.level_rows[d][k] += (int64_t)c[k];
-                r->stats.level_bytes[d] += b_gather + b_pull + b_heavy + b_hub;
-                r->stats.level_sparse[d] = (int32_t)c[cDirRows];
-            }
-            if (!opush_level && !fc_level) r->stats.launches[HGX_K_LINK_GATHER] += 1;
-            r->stats.launches[pull_kind] += 1;
-            if (d < 64) r->stats.level_new[d] += (int64_t)c[cNewAtoms];
-        }
+        for (int d = 0; d < nexp; ++d)
+            account_level(r, bt, mode, d, level_ctr[before + d],
+                          (double)(d == 0 ? bt.S : level_ctr[before + d - 1].c[cNewAtoms]));
         r->stats.count_pass_levels += bt.pass_levels;
-        r->batches.push_back(std::move(bt));
     }
     if (tm.on) HGX_HIP(hipEventRecord(tm.all.b, g->stream));
     spin_sync(g->stream);
@@ -6337,16 +6357,10 @@ void hgx_bfs_result_free(hgx_bfs_result* r) {
 // pull levels), the ordered-mode yield flags and the frontier-push chunk table -- built now on the
 // snapshot so that its execution contexts (hgx_graph_context) share one copy.  Caller holds g->mu.
 void hgx::bfs_shared_tables(hgx_graph* g) {
-    hipStream_t s = g->stream;
-    const int64_t A = g->A;
-    if (!g->hasinc) {
-        HGX_HIP(hipMalloc(&g->hasinc, sizeof(u64) * (size_t)(ceil_div(A, 64) + 1)));
-        hgx_hasinc<<<grid_for(ceil_div(A, 64) * 64, 256, 4096), 256, 0, s>>>(A, g->inc_off, (u64*)g->hasinc);
-        HGX_CHECK_LAUNCH();
-    }
-    if (!g->inc_yf) ensure_inc_yield(g);
-    if (g->n_pchunks < 0) build_push_chunks(g);
-    HGX_HIP(hipStreamSynchronize(s));
+    ensure_hasinc(g, g->stream);
+    ensure_inc_yield(g);
+    ensure_push_chunks(g);
+    HGX_HIP(hipStreamSynchronize(g->stream));
 }
 
 void hgx::ensure_inc_yield(hgx_graph* g) {

@@ -35,21 +35,6 @@ namespace {
 
 constexpr u64 kNoKey = ~0ull;
 
-enum Mode { kSym = 0, kAfterFirst = 1, kBeforeFirst = 2, kBeforeLast = 3, kAfterLast = 4 };
-
-// Mirrors pyref.mode_of (as hgx_bfs.hip).
-int mode_of(const hgx_algen_opts& o) {
-    bool P = o.return_preceding, S = o.return_succeeding, R = o.reverse_order, RS = o.return_source;
-    if (!R) {
-        if (!P) return kAfterFirst;
-        if (!S && !RS) return kBeforeFirst;
-        return kSym;
-    }
-    if (!P) return kBeforeLast;
-    if (!S && !RS) return kAfterLast;
-    return kSym;
-}
-
 // Device words of one call.
 enum { cEntries = 0, cPins = 1, cFaProbes = 2, cRowProbes = 3, cWords = 8 };
 

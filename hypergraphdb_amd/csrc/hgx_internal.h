@@ -210,6 +210,18 @@ struct Transport {
     virtual void compute_release(hipStream_t) {}   // end of the work or an error path: give the gate back
     virtual const char* kind() const = 0;
 };
+// A part's device work between compute_begin and compute_release (tr may be null: one part); the gate is given
+// back on an error path too.
+struct ComputeGate {
+    Transport* tr;
+    hipStream_t s;
+    ComputeGate(Transport* t, hipStream_t st) : tr(t), s(st) {
+        if (tr) tr->compute_begin(s);
+    }
+    ~ComputeGate() {
+        if (tr) tr->compute_release(s);
+    }
+};
 
 // Cross-thread coalescing of pattern batches (hgx_pattern_batch_packed, HGX_OPT_QUERY_COALESCE):
 // a caller that finds the graph's device busy queues its batch; whoever runs next takes every queued
@@ -456,6 +468,55 @@ inline void spin_sync(hipStream_t s) {
     while ((e = hipStreamQuery(s)) == hipErrorNotReady) {
     }
     HGX_HIP(e);
+}
+// As spin_sync for one event (the blocking wait adds tens of microseconds per BFS level, and unbounded
+// traversals run tens of short levels).
+inline void spin_event(hipEvent_t ev) {
+    hipError_t e;
+    while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
+    }
+    HGX_HIP(e);
+}
+// Waits for a word of mapped host memory that a kernel on s stores `want` into, by polling.  The stream is
+// asked every 1024 polls: one that finished or failed without the word is an error (HGX_E_DEVICE, `what`).
+inline void wait_host_word(const u64* word, u64 want, hipStream_t s, const char* what) {
+    for (unsigned spin = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) != want; ++spin) {
+        if ((spin & 1023u) != 1023u) continue;
+        const hipError_t e = hipStreamQuery(s);
+        if (e == hipErrorNotReady) continue;
+        if (e != hipSuccess) HGX_HIP(e);
+        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != want) fail(HGX_E_DEVICE, what);
+    }
+}
+// Device buffers of one call or one batch from the graph's pool, given back at scope exit (an error path
+// included; the caller holds g->mu).  Releasing into the pool is stream-ordered: no synchronisation.
+struct PoolScratch {
+    hgx_graph* g;
+    std::vector<std::pair<void*, size_t>> t;
+    void* take(size_t bytes) {
+        t.emplace_back(nullptr, bytes);   // the slot first: a failed allocation of either kind strands nothing
+        return t.back().first = g->alloc(bytes);
+    }
+    void give_back() {   // now, and the object is empty again (its capacity stays)
+        for (auto& x : t)
+            if (x.first) g->release(x.first, x.second);
+        t.clear();
+    }
+    ~PoolScratch() { give_back(); }
+};
+// The generator's closed-form neighbour rule as a mode (every engine's kernels switch on it).
+enum Mode { kSym = 0, kAfterFirst = 1, kBeforeFirst = 2, kBeforeLast = 3, kAfterLast = 4 };
+// Mirrors pyref.mode_of (validated exhaustively against the DefaultALGenerator restatement).
+inline int mode_of(const hgx_algen_opts& o) {
+    bool P = o.return_preceding, S = o.return_succeeding, R = o.reverse_order, RS = o.return_source;
+    if (!R) {
+        if (!P) return kAfterFirst;
+        if (!S && !RS) return kBeforeFirst;
+        return kSym;
+    }
+    if (!P) return kBeforeLast;
+    if (!S && !RS) return kAfterLast;
+    return kSym;
 }
 inline int grid_for(int64_t work_items, int block, int max_blocks = 8192) {
     int64_t b = ceil_div(work_items > 0 ? work_items : 1, block);

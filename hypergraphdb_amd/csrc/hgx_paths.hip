@@ -43,21 +43,6 @@ constexpr int kPairShift = 44, kSubShift = 32;
 constexpr int64_t kMaxChunkPairs = (int64_t)1 << 20;
 constexpr int64_t kMaxSubs = 4096;
 
-enum Mode { kSym = 0, kAfterFirst = 1, kBeforeFirst = 2, kBeforeLast = 3, kAfterLast = 4 };
-
-// Mirrors pyref.mode_of (as hgx_bfs.hip).
-int mode_of(const hgx_algen_opts& o) {
-    bool P = o.return_preceding, S = o.return_succeeding, R = o.reverse_order, RS = o.return_source;
-    if (!R) {
-        if (!P) return kAfterFirst;
-        if (!S && !RS) return kBeforeFirst;
-        return kSym;
-    }
-    if (!P) return kBeforeLast;
-    if (!S && !RS) return kAfterLast;
-    return kSym;
-}
-
 // Device words of one call: two frontier counters, then the statistics and flags.
 enum { cCnt0 = 0, cCnt1 = 1, cExpanded = 2, cEntries = 3, cRelaxed = 4, cImproved = 5, cOverflow = 6, cChanged = 7,
        cPlateau = 8, cWords = 16 };

@@ -1923,15 +1923,7 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         }
         ev.rec(3, s);
         if (flag) {
-            const u64* fl = (const u64*)(hm + m_stat) + 7;
-            for (unsigned spin = 0; __atomic_load_n(fl, __ATOMIC_ACQUIRE) != flag_seq; ++spin) {
-                if ((spin & 1023u) != 1023u) continue;   // the stream is asked every 1024 polls
-                const hipError_t e = hipStreamQuery(s);
-                if (e == hipErrorNotReady) continue;
-                if (e != hipSuccess) HGX_HIP(e);
-                if (__atomic_load_n(fl, __ATOMIC_ACQUIRE) != flag_seq)
-                    fail(HGX_E_DEVICE, "hgx_pattern_batch: the completion flag never arrived");
-            }
+            wait_host_word((const u64*)(hm + m_stat) + 7, flag_seq, s, "hgx_pattern_batch: the completion flag never arrived");
         } else {
             spin_sync(s);
         }

@@ -36,18 +36,6 @@ namespace hgx {
 
 namespace {
 
-// Buffers taken from the graph pool for the index build, given back on every exit path.
-struct PoolScratch {
-    hgx_graph* g;
-    std::vector<std::pair<void*, size_t>> t;
-    void* take(size_t bytes) {
-        void* p = g->alloc(bytes);
-        t.push_back({p, bytes});
-        return p;
-    }
-    ~PoolScratch() { for (auto& x : t) g->release(x.first, x.second); }
-};
-
 __global__ void __launch_bounds__(256) k_ti_iota(int64_t M, int32_t* __restrict__ row) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (int64_t)gridDim.x * blockDim.x)
         row[i] = (int32_t)i;

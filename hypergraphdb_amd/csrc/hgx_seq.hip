@@ -49,21 +49,6 @@ namespace {
 typedef unsigned long long u64;
 constexpr u64 kNoKey = ~0ull;
 
-enum SeqMode { sSym = 0, sAfterFirst = 1, sBeforeFirst = 2, sBeforeLast = 3, sAfterLast = 4 };
-
-// Same closed-form rule as the bitset engine (hgx_bfs.hip mode_of; pyref.mode_of).
-int seq_mode(const hgx_algen_opts& o) {
-    bool P = o.return_preceding, S = o.return_succeeding, R = o.reverse_order, RS = o.return_source;
-    if (!R) {
-        if (!P) return sAfterFirst;
-        if (!S && !RS) return sBeforeFirst;
-        return sSym;
-    }
-    if (!P) return sBeforeLast;
-    if (!S && !RS) return sAfterLast;
-    return sSym;
-}
-
 int bitlen(u64 x) { return x ? 64 - __builtin_clzll(x) : 0; }
 
 // Host-side phase trace of hgx_bfs_sequence (HGX_SEQ_TRACE=1): microseconds since the call began.
@@ -139,16 +124,16 @@ __device__ __forceinline__ int32_t ya_entry(const YaArgs& a, int32_t p, int64_t 
     const int32_t n = (int32_t)(a.tgt_off[L + 1] - b);
     if (n < a.min_arity) return 0;                           // minArity (:309)
     hi = n;
-    if (a.mode != sSym) {
+    if (a.mode != kSym) {
         int32_t fv = -1, lv = -1;
         for (int32_t q = 0; q < n; ++q)
             if (a.tgt_idx[b + q] == p) {
                 if (fv < 0) fv = q;
                 lv = q;
             }
-        if (a.mode == sAfterFirst) lo = fv + 1;
-        else if (a.mode == sBeforeFirst) hi = fv;
-        else if (a.mode == sBeforeLast) hi = lv;
+        if (a.mode == kAfterFirst) lo = fv + 1;
+        else if (a.mode == kBeforeFirst) hi = fv;
+        else if (a.mode == kBeforeLast) hi = lv;
         else lo = lv + 1;
     }
     int32_t c = 0;
@@ -341,16 +326,16 @@ __global__ void __launch_bounds__(256) hgx_seq_expand(ExpandArgs a) {
                 n = (int32_t)(a.tgt_off[L + 1] - b);
                 if (n >= a.min_arity) {                                           // minArity (:309)
                     int32_t hi = n;                                               // yielded positions [lo, hi)
-                    if (a.mode != sSym) {
+                    if (a.mode != kSym) {
                         int32_t fv = -1, lv = -1;
                         for (int32_t q = 0; q < n; ++q)
                             if (a.tgt_idx[b + q] == p) {
                                 if (fv < 0) fv = q;
                                 lv = q;
                             }
-                        if (a.mode == sAfterFirst) lo = fv + 1;
-                        else if (a.mode == sBeforeFirst) hi = fv;
-                        else if (a.mode == sBeforeLast) hi = lv;
+                        if (a.mode == kAfterFirst) lo = fv + 1;
+                        else if (a.mode == kBeforeFirst) hi = fv;
+                        else if (a.mode == kBeforeLast) hi = lv;
                         else lo = lv + 1;
                     }
                     cnt = hi > lo ? hi - lo : 0;
@@ -704,7 +689,7 @@ __device__ void sb_process(SbShared& sm, const SbArgs& a, int F, int cn, int64_t
 #pragma unroll
             for (int q = 0; q < 8; ++q) tg[q] = q < n ? a.tgt_idx[b + q] : -1;
             int32_t lo = 0, hi = n;
-            if (a.mode != sSym) {
+            if (a.mode != kSym) {
                 int32_t fv = -1, lv = -1;
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
@@ -712,9 +697,9 @@ __device__ void sb_process(SbShared& sm, const SbArgs& a, int F, int cn, int64_t
                         if (fv < 0) fv = q;
                         lv = q;
                     }
-                if (a.mode == sAfterFirst) lo = fv + 1;
-                else if (a.mode == sBeforeFirst) hi = fv;
-                else if (a.mode == sBeforeLast) hi = lv;
+                if (a.mode == kAfterFirst) lo = fv + 1;
+                else if (a.mode == kBeforeFirst) hi = fv;
+                else if (a.mode == kBeforeLast) hi = lv;
                 else lo = lv + 1;
             }
 #pragma unroll
@@ -723,16 +708,16 @@ __device__ void sb_process(SbShared& sm, const SbArgs& a, int F, int cn, int64_t
                     sb_insert(sm, tg[q], ((kb + (u64)(a.rev ? n - 1 - q : q)) << 32) | lw);
         } else {
             int32_t lo = 0, hi = n;
-            if (a.mode != sSym) {
+            if (a.mode != kSym) {
                 int32_t fv = -1, lv = -1;
                 for (int32_t q = 0; q < n; ++q)
                     if (a.tgt_idx[b + q] == p) {
                         if (fv < 0) fv = q;
                         lv = q;
                     }
-                if (a.mode == sAfterFirst) lo = fv + 1;
-                else if (a.mode == sBeforeFirst) hi = fv;
-                else if (a.mode == sBeforeLast) hi = lv;
+                if (a.mode == kAfterFirst) lo = fv + 1;
+                else if (a.mode == kBeforeFirst) hi = fv;
+                else if (a.mode == kBeforeLast) hi = lv;
                 else lo = lv + 1;
             }
             for (int32_t q = lo; q < hi; ++q) {
@@ -1211,7 +1196,7 @@ __device__ void bb_process(BbShared& sm, const BbArgs& a, int F, int cn, int64_t
 #pragma unroll
             for (int q = 0; q < 8; ++q) tg[q] = q < n ? a.tgt_idx[b + q] : -1;
             int32_t lo = 0, hi = n;
-            if (a.mode != sSym) {
+            if (a.mode != kSym) {
                 int32_t fv = -1, lv = -1;
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
@@ -1219,9 +1204,9 @@ __device__ void bb_process(BbShared& sm, const BbArgs& a, int F, int cn, int64_t
                         if (fv < 0) fv = q;
                         lv = q;
                     }
-                if (a.mode == sAfterFirst) lo = fv + 1;
-                else if (a.mode == sBeforeFirst) hi = fv;
-                else if (a.mode == sBeforeLast) hi = lv;
+                if (a.mode == kAfterFirst) lo = fv + 1;
+                else if (a.mode == kBeforeFirst) hi = fv;
+                else if (a.mode == kBeforeLast) hi = lv;
                 else lo = lv + 1;
             }
 #pragma unroll
@@ -1229,16 +1214,16 @@ __device__ void bb_process(BbShared& sm, const BbArgs& a, int F, int cn, int64_t
                 if (q >= lo && q < hi && tg[q] != p) bb_insert(sm, tg[q]);
         } else {
             int32_t lo = 0, hi = n;
-            if (a.mode != sSym) {
+            if (a.mode != kSym) {
                 int32_t fv = -1, lv = -1;
                 for (int32_t q = 0; q < n; ++q)
                     if (a.tgt_idx[b + q] == p) {
                         if (fv < 0) fv = q;
                         lv = q;
                     }
-                if (a.mode == sAfterFirst) lo = fv + 1;
-                else if (a.mode == sBeforeFirst) hi = fv;
-                else if (a.mode == sBeforeLast) hi = lv;
+                if (a.mode == kAfterFirst) lo = fv + 1;
+                else if (a.mode == kBeforeFirst) hi = fv;
+                else if (a.mode == kBeforeLast) hi = lv;
                 else lo = lv + 1;
             }
             for (int32_t q = lo; q < hi; ++q) {
@@ -1274,7 +1259,7 @@ __device__ void bb_run(BbShared& sm, const BbArgs& a, int si) {
         // frontier offsets (+ the yield lists'), streamed yield flags
         nbytes += tid == 0 ? (a.y_off ? 32 * (int64_t)F : 16 * (int64_t)F + (a.yf ? T : 0)) : 0;
         if (T == 0) break;
-        if (T > (a.mode != sSym ? kBbItemLimit : kBbItemLimitSym)) {
+        if (T > (a.mode != kSym ? kBbItemLimit : kBbItemLimitSym)) {
             ovf = true;
             break;
         }
@@ -1834,17 +1819,17 @@ __global__ void __launch_bounds__(NT) hgx_bfs_coop(CoArgs a) {
                         nbytes += 16 + 4 * (int64_t)n;
                         act = n >= a.min_arity;                              // minArity (:309)
                         int32_t fv = -1, lv = -1;
-                        if (act && a.mode != sSym)
+                        if (act && a.mode != kSym)
                             for (int32_t q = 0; q < n; ++q)
                                 if (a.tgt_idx[tb + q] == p) {
                                     if (fv < 0) fv = q;
                                     lv = q;
                                 }
                         qhi = n;
-                        if (a.mode == sAfterFirst) qlo = fv + 1;
-                        else if (a.mode == sBeforeFirst) qhi = fv;
-                        else if (a.mode == sBeforeLast) qhi = lv;
-                        else if (a.mode == sAfterLast) qlo = lv + 1;
+                        if (a.mode == kAfterFirst) qlo = fv + 1;
+                        else if (a.mode == kBeforeFirst) qhi = fv;
+                        else if (a.mode == kBeforeLast) qhi = lv;
+                        else if (a.mode == kAfterLast) qlo = lv + 1;
                         if (!act) qhi = qlo;
                     }
                 }
@@ -2452,16 +2437,16 @@ __global__ void __launch_bounds__(256) hgx_ls_expand(LsArgs a, int32_t d) {
         }
         if (live && !a.a_tgt) {
             hi = n;
-            if (a.mode != sSym) {
+            if (a.mode != kSym) {
                 int32_t fv = -1, lv = -1;
                 for (int32_t q = 0; q < n; ++q)
                     if (a.tgt_idx[b + q] == p) {
                         if (fv < 0) fv = q;
                         lv = q;
                     }
-                if (a.mode == sAfterFirst) lo = fv + 1;
-                else if (a.mode == sBeforeFirst) hi = fv;
-                else if (a.mode == sBeforeLast) hi = lv;
+                if (a.mode == kAfterFirst) lo = fv + 1;
+                else if (a.mode == kBeforeFirst) hi = fv;
+                else if (a.mode == kBeforeLast) hi = lv;
                 else lo = lv + 1;
             }
         }
@@ -2605,10 +2590,10 @@ __device__ __forceinline__ int lp_hits_count(const LsArgs& a, int32_t t, int64_t
         for (int q2 = q + 1; q2 < 8; ++q2)
             if (c.tg[q2] == p) lp = q2;
         int32_t lo = 0, hi = n;   // positions p yields (3.2)
-        if (a.mode == sAfterFirst) lo = q + 1;
-        else if (a.mode == sBeforeFirst) hi = q;
-        else if (a.mode == sBeforeLast) hi = lp;
-        else if (a.mode == sAfterLast) lo = lp + 1;
+        if (a.mode == kAfterFirst) lo = q + 1;
+        else if (a.mode == kBeforeFirst) hi = q;
+        else if (a.mode == kBeforeLast) hi = lp;
+        else if (a.mode == kAfterLast) lo = lp + 1;
         int32_t qt = -1;   // t's best yielded position
 #pragma unroll
         for (int q2 = 0; q2 < 8; ++q2)
@@ -2638,10 +2623,10 @@ __device__ __forceinline__ void lp_long_row(const LsArgs& a, int32_t t, int64_t 
         for (int32_t q2 = q + 1; q2 < n; ++q2)
             if (a.tgt_idx[tb + q2] == p) lp = q2;
         int32_t lo = 0, hi = n;
-        if (a.mode == sAfterFirst) lo = q + 1;
-        else if (a.mode == sBeforeFirst) hi = q;
-        else if (a.mode == sBeforeLast) hi = lp;
-        else if (a.mode == sAfterLast) lo = lp + 1;
+        if (a.mode == kAfterFirst) lo = q + 1;
+        else if (a.mode == kBeforeFirst) hi = q;
+        else if (a.mode == kBeforeLast) hi = lp;
+        else if (a.mode == kAfterLast) lo = lp + 1;
         int32_t qt = -1;
         for (int32_t q2 = lo; q2 < hi; ++q2)
             if (a.tgt_idx[tb + q2] == t && (qt < 0 || a.rev)) qt = q2;
@@ -4162,20 +4147,6 @@ __global__ void __launch_bounds__(NT) hgx_seq_coop(ScArgs a) {
     }
 }
 
-// Device buffers of one call, given back to the graph's pool at scope exit.
-struct SeqScratch {
-    hgx_graph* g;
-    std::vector<std::pair<void*, size_t>> t;
-    void* take(size_t bytes) {
-        void* p = g->alloc(bytes);
-        t.push_back({p, bytes});
-        return p;
-    }
-    ~SeqScratch() {
-        for (auto& x : t) g->release(x.first, x.second);
-    }
-};
-
 template <class T> struct DevBuf {
     hgx_graph* g;
     T* p = nullptr;
@@ -4406,7 +4377,7 @@ void seq_levels(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max
             int64_t* dlist = list.get(cap);
             HGX_HIP(hipMemsetAsync(dcnt, 0, sizeof(u64), st));
             ExpandArgs ea{T, F, dpre, cur_a, cur_s, e_base, A, g->inc_off, g->inc_row, g->inc_type, g->tgt_off,
-                          g->tgt_idx, o.link_type, o.return_source ? 1 : 2, seq_mode(o), o.reverse_order ? 1 : 0,
+                          g->tgt_idx, o.link_type, o.return_source ? 1 : 2, mode_of(o), o.reverse_order ? 1 : 0,
                           sh_e, sh_j, dkey, dlist, dcnt, cap};
             hgx_seq_expand<<<grid_for(ceil_div(T, 256) * 256, 256, 16384), 256, 0, st>>>(ea);
             HGX_CHECK_LAUNCH();
@@ -4550,7 +4521,7 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
                        SeqOut& out, int64_t seed0) {
     hipStream_t st = g->stream;
     const int64_t A = g->A;
-    const int mode = seq_mode(o);
+    const int mode = mode_of(o);
     // pull levels (HGX_OPT_SEQ_PULL: 0 never, 1 by the level's width (default), 2 every level -- tests) read
     // the incidence items; with the yield adjacency the items are its pairs and every level pushes
     // (forced pulls drop the adjacency, so the tests reach the pull in every generator mode)
@@ -4603,7 +4574,7 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
         }
         a.inc_row = g->inc_row;
         a.inc_type = g->inc_type;
-        a.yf = mode != sSym ? g->inc_yf : nullptr;
+        a.yf = mode != kSym ? g->inc_yf : nullptr;
         a.tgt_off = g->tgt_off;
         a.tgt_idx = g->tgt_idx;
         a.link_atom = g->link_atom;
@@ -4623,7 +4594,7 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
         a.tcap = tcap;
         a.rcap = rcap;
         a.hflag = hflag_d;
-        SeqScratch w{g, {}};
+        PoolScratch w{g, {}};
         const size_t rows = sizeof(u64) * (size_t)A * (size_t)W;
         a.vis = (u64*)w.take(rows);
         a.ctl = (int64_t*)w.take(sizeof(int64_t) * kLsCtlWords);
@@ -4793,16 +4764,6 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
                 for (auto& x : *v) g->seq_hbufs.push_back(x.b);
             }
         } give_back{g, cs, &lbufs};
-        // waits for a mapped word the device stores with seq (the stream is asked every 1024 polls)
-        auto wait_seq = [&](const u64* p, u64 want, const char* what) {
-            for (unsigned spin = 0; __atomic_load_n(p, __ATOMIC_ACQUIRE) != want; ++spin) {
-                if ((spin & 1023u) != 1023u) continue;
-                const hipError_t e = hipStreamQuery(st);
-                if (e == hipErrorNotReady) continue;
-                if (e != hipSuccess) HGX_HIP(e);
-                if (__atomic_load_n(p, __ATOMIC_ACQUIRE) != want) fail(HGX_E_DEVICE, std::string("hgx_bfs_sequence: ") + what);
-            }
-        };
         auto copy_level = [&](int32_t d, int64_t out0, int64_t n) {
             const u64* bnd = g->seq_flag + 8 + (kLrParts + 1) * (d & 1);
             if (n < a.pack_min) {
@@ -4837,7 +4798,7 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
                 if (b < 0 || e > n || e < b) fail(HGX_E_DEVICE, "hgx_bfs_sequence: rank-part bounds inconsistent");
                 if (e == b) continue;
                 const u64* hp = g->seq_flag + kPackWords + 2 * ((d & 1) * kLrParts + q);
-                wait_seq(hp + 1, base + (u64)d + 1, "a packed part's run count never arrived");
+                wait_host_word(hp + 1, base + (u64)d + 1, st, "hgx_bfs_sequence: a packed part's run count never arrived");
                 const int64_t runs = (int64_t)__atomic_load_n(hp, __ATOMIC_RELAXED);
                 const int64_t np = e - b, pw = (np + 63) / 64, pbk = (np + kLpBlk - 1) / kLpBlk;
                 if (runs < 1 || runs > np) fail(HGX_E_DEVICE, "hgx_bfs_sequence: packed part inconsistent");
@@ -4877,14 +4838,7 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
             if (enq < maxd && enq == dw + 1) enqueue(enq++);   // one level ahead of the host
             const u64 want = base + (u64)dw + 1;
             const u64* hf = g->seq_flag + 4 * (dw & 1);
-            for (unsigned spin = 0; __atomic_load_n(hf + 2, __ATOMIC_ACQUIRE) != want; ++spin) {
-                if ((spin & 1023u) != 1023u) continue;   // the stream is asked every 1024 polls
-                const hipError_t e = hipStreamQuery(st);
-                if (e == hipErrorNotReady) continue;
-                if (e != hipSuccess) HGX_HIP(e);
-                if (__atomic_load_n(hf + 2, __ATOMIC_ACQUIRE) != want)
-                    fail(HGX_E_DEVICE, "hgx_bfs_sequence: a level's size never arrived");
-            }
+            wait_host_word(hf + 2, want, st, "hgx_bfs_sequence: a level's size never arrived");
             const int64_t n = (int64_t)__atomic_load_n(hf, __ATOMIC_RELAXED);
             status = (int64_t)__atomic_load_n(hf + 1, __ATOMIC_RELAXED);
             if (status) break;
@@ -5063,7 +5017,7 @@ bool co_fits(hgx_graph* g) {
 // pools with it unless the result took the pairs.
 struct CoRun {
     hgx_graph* g;
-    SeqScratch sc;
+    PoolScratch sc;
     CoArgs a{};
     int2* pairs = nullptr;
     int64_t pcap = 0;
@@ -5087,7 +5041,7 @@ struct CoRun {
 // seeds); the control words are cleared on the stream.
 void co_setup(hgx_graph* g, CoRun& r, int32_t k, int32_t kcap, int32_t max_depth, const hgx_algen_opts& o) {
     hipStream_t st = g->stream;
-    const int mode = seq_mode(o);
+    const int mode = mode_of(o);
     const int64_t vwords = g->A / 64 + 1;
     if (g->co_vis_seeds < kcap) {   // zero-invariant bitmaps, grown to the seed count
         if (g->co_vis) HGX_HIP(hipFree(g->co_vis));
@@ -5129,7 +5083,7 @@ void co_setup(hgx_graph* g, CoRun& r, int32_t k, int32_t kcap, int32_t max_depth
     a.inc_off = g->inc_off;
     a.inc_row = g->inc_row;
     a.inc_type = g->inc_type;
-    a.yf = mode != sSym ? g->inc_yf : nullptr;
+    a.yf = mode != kSym ? g->inc_yf : nullptr;
     stage_items(g, mode, o, a);
     a.tgt_off = g->tgt_off;
     a.tgt_idx = g->tgt_idx;
@@ -5319,7 +5273,7 @@ constexpr int32_t kSeqChainMin = 64;   // seeds of a call from which the grid st
 // separates the two stages).
 struct ScRun {
     hgx_graph* g;
-    SeqScratch w;
+    PoolScratch w;
     ScArgs a{};
     int nblk = 0;
     bool trace = false;
@@ -5490,7 +5444,7 @@ struct ScRun {
 // when a capacity or the grid did not fit -- the caller runs the level engine.
 bool seq_coop(hgx_graph* g, const int32_t* seeds, const std::vector<int32_t>& sidx, int32_t maxd,
               const hgx_algen_opts& o, SeqOut& out, double* ms) {
-    const int mode = seq_mode(o);
+    const int mode = mode_of(o);
     const YieldAdj* ya = stage_yield_adj(g, mode, o);
     const int32_t k = (int32_t)sidx.size();
     if (!ya || k == 0 || k > kMaxCoSeeds || !sc_fits(g)) return false;
@@ -5523,8 +5477,8 @@ void bfs_block(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_
         BlockSet& out;
         ~Fallbacks() { out.co_fallbacks = (int32_t)(g->co_timeouts - t0); }
     } fb{g, timeouts0, out};
-    const int mode = seq_mode(o);
-    if (mode != sSym) ensure_inc_yield(g);
+    const int mode = mode_of(o);
+    if (mode != kSym) ensure_inc_yield(g);
     out.seeds.assign(seeds, seeds + n_seeds);
     out.atoms.assign((size_t)n_seeds, nullptr);
     out.lcnt.assign((size_t)n_seeds, nullptr);
@@ -5534,7 +5488,7 @@ void bfs_block(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_
     a.inc_off = g->inc_off;
     a.inc_row = g->inc_row;
     a.inc_type = g->inc_type;
-    a.yf = mode != sSym ? g->inc_yf : nullptr;
+    a.yf = mode != kSym ? g->inc_yf : nullptr;
     a.tgt_off = g->tgt_off;
     a.tgt_idx = g->tgt_idx;
     a.want_type = o.link_type;
@@ -5686,14 +5640,14 @@ void free_yield_lists(hgx_graph* g) {
 }
 
 const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arity, bool rev) {
-    if (mode == sSym && type < 0) return nullptr;   // every co-target of every entry: too large to keep
+    if (mode == kSym && type < 0) return nullptr;   // every co-target of every entry: too large to keep
     hgx_graph* root = g->base ? g->base : g;         // built once on the snapshot, read by its contexts
     std::lock_guard<std::mutex> lk(root->ylist_mu);
     for (const YieldAdj& y : root->yadjs)
         if (y.mode == mode && y.type == type && y.min_arity == min_arity && y.rev == (int32_t)rev)
             return y.off ? &y : nullptr;
     if (root->yadjs.size() >= kMaxYieldLists) return nullptr;
-    if (mode != sSym) ensure_inc_yield(g);
+    if (mode != kSym) ensure_inc_yield(g);
     hipStream_t st = g->stream;
     const int64_t A = g->A;
     YaArgs a{};
@@ -5701,7 +5655,7 @@ const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arit
     a.inc_off = g->inc_off;
     a.inc_row = g->inc_row;
     a.inc_type = g->inc_type;
-    a.yf = mode != sSym ? g->inc_yf : nullptr;
+    a.yf = mode != kSym ? g->inc_yf : nullptr;
     a.tgt_off = g->tgt_off;
     a.tgt_idx = g->tgt_idx;
     a.link_atom = g->link_atom;
@@ -5743,19 +5697,19 @@ const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arit
 }
 
 const YieldList* yield_list(hgx_graph* g, int mode, int32_t type) {
-    if (mode == sSym && type < 0) return nullptr;   // every entry: the incidence itself
+    if (mode == kSym && type < 0) return nullptr;   // every entry: the incidence itself
     hgx_graph* root = g->base ? g->base : g;         // built once on the snapshot, read by its contexts
     std::lock_guard<std::mutex> lk(root->ylist_mu);
     for (const YieldList& y : root->ylists)
         if (y.mode == mode && y.type == type) return &y;
     if (root->ylists.size() >= kMaxYieldLists) return nullptr;   // the streamed flags instead
-    if (mode != sSym) ensure_inc_yield(g);
+    if (mode != kSym) ensure_inc_yield(g);
     hipStream_t st = g->stream;
     const int64_t A = g->A;
     YieldList y{mode, type, nullptr, nullptr, 0};
     HGX_HIP(hipMalloc(&y.off, sizeof(int64_t) * (size_t)(A + 1)));
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((A + 3) / 4, 16384));
-    const uint8_t* yf = mode != sSym ? g->inc_yf : nullptr;
+    const uint8_t* yf = mode != kSym ? g->inc_yf : nullptr;
     int64_t* cnt = (int64_t*)g->alloc(sizeof(int64_t) * (size_t)(A + 1));
     hgx_yl_count<<<grid, 256, 0, st>>>(A, g->inc_off, g->inc_type, yf, mode, type, cnt);
     HGX_CHECK_LAUNCH();
@@ -5900,7 +5854,7 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
     HGX_HIP(hipSetDevice(g->device));
     hipStream_t st = g->stream;
     const int32_t maxd = max_depth < 0 ? INT32_MAX : max_depth;
-    const int mode = seq_mode(o);
+    const int mode = mode_of(o);
 
     hgx_seq_result* r = new hgx_seq_result();
     struct Guard {
@@ -5914,7 +5868,7 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
     r->lev_of.assign((size_t)n_seeds, -1);
     std::vector<int64_t> cnt((size_t)n_seeds, 0);
     seq_maxes(g);
-    if (mode != sSym) ensure_inc_yield(g);
+    if (mode != kSym) ensure_inc_yield(g);
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (g->timing) {
@@ -5932,7 +5886,7 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
         a.inc_off = g->inc_off;
         a.inc_row = g->inc_row;
         a.inc_type = g->inc_type;
-        a.yf = mode != sSym ? g->inc_yf : nullptr;
+        a.yf = mode != kSym ? g->inc_yf : nullptr;
         const YieldAdj* ya = stage_yield_adj(g, mode, o);
         if (ya) {
             a.y_off = ya->off;
