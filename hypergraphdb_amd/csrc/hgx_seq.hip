@@ -1946,6 +1946,10 @@ constexpr int kLsStatus = kLsSlots * kLsSlotWords, kLsTrav = kLsStatus + 1, kLsR
               kLsBytes = kLsStatus + 3, kLsPullN = kLsStatus + 4;
 // status bits: 1 discoveries > cap, 2 runs > rcap, (4 unused since round 5), 8 tiles > tcap, 16 keys wider
 // than 32 bits, 32 push hash too full, 128 a pull pass's hit list overflowed (long rows: rerun pushing)
+// (the host's names for them; the kernels set them by value)
+enum LsStatus : int64_t {
+    kLsDiscFull = 1, kLsRunsFull = 2, kLsTilesFull = 8, kLsKeysWide = 16, kLsHashFull = 32, kLsPullHitsFull = 128
+};
 // A level's discoveries go to kLsDSegs segments of the list, one counter each (a wave appends to the
 // segment of its block): one shared counter took one same-address atomic per wave and round, which
 // serialise at ~20 ns each -- the whole of a config-2 level's expand time.
@@ -4182,6 +4186,36 @@ struct Seg {
     int64_t pi = 0;
     int32_t ab = 4;               // packed: bytes an atom (3: 24-bit little-endian ids; atom is then a byte address)
     hipEvent_t ready = nullptr;   // the copy into its buffer (level engine): readers wait for it
+
+    // separate link / atom (/ dist) arrays; dist = nullptr: every pair has distance dist_c
+    static Seg plain(const int32_t* link, const int32_t* atom, const int32_t* dist, int64_t n, int32_t dist_c) {
+        Seg s{};
+        s.link = link;
+        s.atom = atom;
+        s.dist = dist;
+        s.n = n;
+        s.dist_c = dist_c;
+        return s;
+    }
+    static Seg none() { return plain(nullptr, nullptr, nullptr, -1, 0); }   // (a seed another engine finished)
+    static Seg interleaved(const int32_t* pairs, int64_t n, int32_t dist_c, hipEvent_t ready) {
+        Seg s = plain(pairs, pairs + 1, nullptr, n, dist_c);
+        s.stride = 2;
+        s.ready = ready;
+        return s;
+    }
+    // n pairs of a packed rank part from its pair pi on; atoms: the address of the first one's ab bytes
+    static Seg packed(const int32_t* run_links, const u64* flags, const uint32_t* bb, int64_t pi, const void* atoms,
+                      int32_t ab, int64_t n, int32_t dist_c, hipEvent_t ready) {
+        Seg s = plain(run_links, (const int32_t*)atoms, nullptr, n, dist_c);
+        s.stride = 0;
+        s.flags = flags;
+        s.bb = bb;
+        s.pi = pi;
+        s.ab = ab;
+        s.ready = ready;
+        return s;
+    }
 };
 
 // n pairs of a segment from index so on into links / atoms (either may be null): two copies, or one pass
@@ -4268,6 +4302,71 @@ hipEvent_t ev_take(hgx_graph* g) {
 }
 void ev_give(hgx_graph* g, hipEvent_t e) {
     if (e) g->ev_pool.push_back(e);
+}
+
+// Device time of a stretch of g's stream when the graph has timing on (every method is a no-op otherwise): two
+// pooled events, and a third for a mark in between; they go back to the pool with the object unless the result
+// took them over for a lazy read.
+struct EvTimer {
+    hgx_graph* g;
+    hipEvent_t e0 = nullptr, e1 = nullptr, em = nullptr;
+    explicit EvTimer(hgx_graph* gg) : g(gg) {}
+    EvTimer(const EvTimer&) = delete;
+    EvTimer& operator=(const EvTimer&) = delete;
+    ~EvTimer() {
+        ev_give(g, e0);
+        ev_give(g, e1);
+        ev_give(g, em);
+    }
+    bool on() const { return e0 != nullptr; }
+    void start() {
+        if (!g->timing) return;
+        e0 = ev_take(g);
+        e1 = ev_take(g);
+        HGX_HIP(hipEventRecord(e0, g->stream));
+    }
+    void mark() {
+        if (!on()) return;
+        em = ev_take(g);
+        HGX_HIP(hipEventRecord(em, g->stream));
+    }
+    void stop() {
+        if (on()) HGX_HIP(hipEventRecord(e1, g->stream));
+    }
+    // once the stream has been waited for
+    static float between(hipEvent_t a, hipEvent_t b) {
+        float ms = 0;
+        HGX_HIP(hipEventElapsedTime(&ms, a, b));
+        return ms;
+    }
+    float ms() const { return on() ? between(e0, e1) : 0.f; }
+    float ms_to_mark() const { return em ? between(e0, em) : 0.f; }
+    float ms_from_mark() const { return em ? between(em, e1) : 0.f; }
+    // The end of the stretch.  lazy (work behind the end is still running and the caller must not wait): the
+    // events go to lz0 / lz1, whose owner reads and destroys them later; else waits for the end and sets *ms.
+    // true when it waited.
+    bool finish(bool lazy, hipEvent_t* lz0, hipEvent_t* lz1, double* ms_out) {
+        if (!on()) return false;
+        stop();
+        if (lazy) {
+            *lz0 = e0;
+            *lz1 = e1;
+            e0 = e1 = nullptr;
+            return false;
+        }
+        HGX_HIP(hipEventSynchronize(e1));
+        *ms_out = ms();
+        return true;
+    }
+};
+
+// out[i] = in[0] + ... + in[i - 1] for i < n on g's stream (the temporary storage from the pool; every use shares
+// one instantiation of the rocPRIM kernels: in is not const)
+void exclusive_scan_i64(hgx_graph* g, int64_t* in, int64_t* out, size_t n) {
+    size_t tb = 0;
+    HGX_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), g->stream));
+    PoolScratch tmp{g, {}};
+    HGX_HIP(rocprim::exclusive_scan(tmp.take(tb), tb, in, out, (int64_t)0, n, rocprim::plus<int64_t>(), g->stream));
 }
 
 // The yield list the workgroup and grid stages read (HGX_YIELD_LISTS=0, for A/B: stream the incidence
@@ -4364,10 +4463,7 @@ void seq_levels(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max
             int64_t* ddeg = pre_in.get(F + 1);
             k_seq_degree<<<grid_for(F + 1, 256), 256, 0, st>>>(F, cur_a, g->inc_off, ddeg);
             HGX_CHECK_LAUNCH();
-            size_t tb = 0;
-            HGX_HIP(rocprim::exclusive_scan(nullptr, tb, ddeg, dpre, (int64_t)0, (size_t)F + 1, rocprim::plus<int64_t>(), st));
-            HGX_HIP(rocprim::exclusive_scan(tmp.get(tb), tb, ddeg, dpre, (int64_t)0, (size_t)F + 1, rocprim::plus<int64_t>(),
-                                            st));
+            exclusive_scan_i64(g, ddeg, dpre, (size_t)F + 1);
             HGX_HIP(hipMemcpyAsync(&h_cnt[0], dpre + F, sizeof(int64_t), hipMemcpyDeviceToHost, st));
             spin_sync(st);
             const int64_t T = (int64_t)h_cnt[0];
@@ -4394,7 +4490,7 @@ void seq_levels(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max
             k_seq_gather_keys<<<grid_for(nn, 256), 256, 0, st>>>(nn, dlist, dkey, dk);
             HGX_CHECK_LAUNCH();
             const int end_bit = std::min(64, sh_e + bitlen(e_base));
-            tb = 0;
+            size_t tb = 0;
             HGX_HIP(rocprim::radix_sort_pairs(nullptr, tb, dk, dks, dlist, dls, (size_t)nn, 0u, (unsigned)end_bit, st));
             HGX_HIP(rocprim::radix_sort_pairs(tmp.get(tb), tb, dk, dks, dlist, dls, (size_t)nn, 0u, (unsigned)end_bit, st));
             int32_t* nxa = na.get(nn);
@@ -4432,7 +4528,7 @@ void seq_levels(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max
         const int32_t* at = lk + lv.nn;
         for (int64_t s = 0; s < lv.nb; ++s) {
             const int64_t n = last[s] - first[s];
-            if (n > 0) out.segs[(size_t)(lv.chunk0 + s)].push_back({lk + first[s], at + first[s], nullptr, n, lv.depth});
+            if (n > 0) out.segs[(size_t)(lv.chunk0 + s)].push_back(Seg::plain(lk + first[s], at + first[s], nullptr, n, lv.depth));
         }
     }
     out.deepest = deepest;
@@ -4514,27 +4610,12 @@ int log2_ceil(int64_t x) {
     return b;
 }
 
-// The level-synchronous engine (hgx_ls_* / hgx_lp_* kernels) over a chunk of <= 1024 seeds; false when
-// a level's keys do not fit 32 bits (the caller splits the chunk).  Capacities start small, grow x4 on
-// overflow and are kept on the graph.
-bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t maxd, const hgx_algen_opts& o,
-                       SeqOut& out, int64_t seed0) {
-    hipStream_t st = g->stream;
-    const int64_t A = g->A;
-    const int mode = mode_of(o);
-    // pull levels (HGX_OPT_SEQ_PULL: 0 never, 1 by the level's width (default), 2 every level -- tests) read
-    // the incidence items; with the yield adjacency the items are its pairs and every level pushes
-    // (forced pulls drop the adjacency, so the tests reach the pull in every generator mode)
-    const int pull_env = std::min(2, std::max(0, (int)g->seq_pull));
-    const YieldAdj* ya = pull_env == 2 ? nullptr : stage_yield_adj(g, mode, o);   // a pair's index is its stream position
-    const int kbits = ya ? 0 : bitlen(g->max_arity > 1 ? (u64)(g->max_arity - 1) : 0);
-    const int32_t W = (nb + 63) / 64;
-    if (W > kLsMaxW) fail(HGX_E_INVALID, "hgx_bfs_sequence: a level-engine chunk holds at most 1024 seeds");
-    const int pull = ya ? 0 : pull_env;
-    bool pull_off = false;   // set when a pull pass overflowed its hit list (rows of > 8 targets)
-    const int32_t* pin_j = pull ? ensure_pin_j(g) : nullptr;
-    hgx_graph* root = g->base ? g->base : g;
-    if (!g->seq_flag) {   // mapped, coherent: the scan kernel's level sizes and rank-part bounds (once per graph)
+// What the level engine keeps on the graph (made on the first call): the mapped, coherent words the scan
+// kernels store level sizes, rank-part bounds and packed counts into, the rank parts' and the copies' events,
+// and the copy streams (packed rank parts alternate between two: two DMA engines side by side; A/B builds:
+// HGX_LS_COPY_STREAMS=1 keeps one).
+void ensure_level_streams(hgx_graph* g, hipStream_t* cs, hipStream_t* cs2) {
+    if (!g->seq_flag) {
         void* hp = nullptr;
         HGX_HIP(hipHostMalloc(&hp, 1024, hipHostMallocMapped | hipHostMallocCoherent));
         std::memset(hp, 0, 1024);
@@ -4547,24 +4628,84 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
     for (hipEvent_t& e : g->ls_ev)
         if (!e) HGX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (!g->stream2) HGX_HIP(hipStreamCreateWithFlags(&g->stream2, hipStreamNonBlocking));
-    hipStream_t cs = g->stream2;   // the pairs' copies to the host, a level (part) at a time
-    // packed rank parts alternate between two copy streams (two DMA engines side by side; A/B builds:
-    // HGX_LS_COPY_STREAMS=1 keeps one)
     static const int ncs = ab_int("HGX_LS_COPY_STREAMS", 2);
     if (ncs > 1 && !g->stream3) HGX_HIP(hipStreamCreateWithFlags(&g->stream3, hipStreamNonBlocking));
-    hipStream_t cs2 = ncs > 1 ? g->stream3 : cs;
-    u64* hflag_d = nullptr;
-    HGX_HIP(hipHostGetDevicePointer((void**)&hflag_d, g->seq_flag, 0));
-    const int64_t full = (int64_t)nb * A;
-    // starting capacities (grown x4 on overflow and kept on the graph); HGX_OPT_SEQ_SMALL (tests) starts
-    // them tiny so that every growth path runs
-    const bool small = g->seq_small != 0;
-    for (int attempt = 0;; ++attempt) {
-        const int64_t cap = std::min(full, std::max<int64_t>(g->ls_cap, small ? 64 : (int64_t)1 << 20));
-        const int64_t tcap = std::max<int64_t>(g->ls_tcap, small ? 8 : (int64_t)1 << 16);
-        const int64_t rcap = std::max<int64_t>(g->ls_rcap, small ? 4 : (int64_t)1 << 14);
-        const int hbits = std::max<int>(log2_ceil(std::max<int64_t>(g->ls_hcap, small ? 64 : (int64_t)1 << 21)), 6);
-        LsArgs a{};
+    *cs = g->stream2;
+    *cs2 = ncs > 1 ? g->stream3 : g->stream2;
+}
+
+// A level's pairs on the host.  Each level's pairs go to the host on the copy stream as soon as the host has
+// read the level's size: a host buffer per level, one copy per rank part after that part's event (the last
+// level's copies overlap its later rank parts and the final runs pass).
+struct LevelPart {   // a packed level's rank part in the level buffer
+    int64_t b, e;
+    const int32_t* link;
+    const u64* flags;
+    const uint32_t* bb;
+    hipEvent_t ready;
+};
+struct LevelBuf {
+    PoolBuf b;
+    int64_t out0, n;
+    bool packed = false;
+    std::vector<LevelPart> parts;
+    int ab = 4;                   // (packed) bytes an atom
+    hipEvent_t ready = nullptr;   // (unpacked: after all its copies)
+};
+
+// One attempt of the level-synchronous engine (hgx_ls_* / hgx_lp_* kernels) over a chunk of <= 1024 seeds:
+// bind, alloc, clear_and_seed, drain; then grow (a capacity was short, or the keys too wide) or keep + assemble.
+// An attempt that is not kept drops its copy events and returns its level buffers once the copies drained.
+struct LevelChunk {
+    enum class Next { kRetry, kSplit };
+    hgx_graph* const g;
+    hgx_graph* const root;
+    const hipStream_t st;
+    hipStream_t cs = nullptr, cs2 = nullptr;   // the pairs' copies to the host, a level (part) at a time
+    const int32_t* const seeds;
+    const int32_t nb, W, maxd;
+    const int64_t A, full;
+    LsArgs a{};
+    PoolScratch w;
+    int64_t cap = 0, tcap = 0, rcap = 0;
+    size_t rows = 0, urows = 0, n_fr = 0;      // bytes of the examined rows, of the union's rows; frontier entries
+    int32_t* dseeds = nullptr;
+    u64 base = 0;                               // the sequence number of the host words before this attempt
+    // the pair copies complete after the call returns (the readers wait per segment): an event after each copy
+    // group, owned by the result
+    std::vector<hipEvent_t> cevs;
+    std::vector<LevelBuf> lbufs;
+    int64_t total = 0;                          // pairs of the levels read so far
+    std::vector<int64_t> ctl;                   // the control words after the last level
+    bool kept = false;
+
+    LevelChunk(hgx_graph* gg, const int32_t* sd, int32_t n, int32_t md)
+        : g(gg), root(gg->base ? gg->base : gg), st(gg->stream), seeds(sd), nb(n), W((n + 63) / 64), maxd(md), A(gg->A),
+          full((int64_t)n * gg->A), w{gg, {}} {
+        if (W > kLsMaxW) fail(HGX_E_INVALID, "hgx_bfs_sequence: a level-engine chunk holds at most 1024 seeds");
+        ensure_level_streams(g, &cs, &cs2);
+    }
+    LevelChunk(const LevelChunk&) = delete;
+    LevelChunk& operator=(const LevelChunk&) = delete;
+    ~LevelChunk() {
+        if (kept) return;
+        if (!lbufs.empty()) {
+            (void)hipStreamSynchronize(cs);
+            std::lock_guard<std::mutex> lk(g->seq_mu);
+            for (auto& x : lbufs) g->seq_hbufs.push_back(x.b);
+        }
+        for (hipEvent_t e : cevs) (void)hipEventDestroy(e);
+    }
+
+    // The graph's and the generator's fields.  Pull levels (HGX_OPT_SEQ_PULL: 0 never, 1 by the level's width
+    // (default), 2 every level -- tests) read the incidence items; with the yield adjacency the items are its
+    // pairs and every level pushes (forced pulls drop the adjacency, so the tests reach the pull in every
+    // generator mode).  pull_off: an earlier attempt's pull pass overflowed its hit list (rows of > 8 targets).
+    void bind(const hgx_algen_opts& o, bool pull_off) {
+        const int mode = mode_of(o);
+        const int pull_env = std::min(2, std::max(0, (int)g->seq_pull));
+        const YieldAdj* ya = pull_env == 2 ? nullptr : stage_yield_adj(g, mode, o);   // a pair's index is its stream position
+        const int pull = ya ? 0 : pull_env;
         a.A = A;
         a.inc_off = g->inc_off;
         if (ya) {
@@ -4582,260 +4723,244 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
         a.min_arity = o.return_source ? 1 : 2;
         a.mode = mode;
         a.rev = o.reverse_order ? 1 : 0;
-        a.kbits = kbits;
-        a.t_limit = std::min<int64_t>(INT32_MAX - 1, (int64_t)(0xFFFFFFFFull >> kbits));
+        a.kbits = ya ? 0 : bitlen(g->max_arity > 1 ? (u64)(g->max_arity - 1) : 0);
+        a.t_limit = std::min<int64_t>(INT32_MAX - 1, (int64_t)(0xFFFFFFFFull >> a.kbits));
         static const int lr_sub = ab_int("HGX_LR_SUB", 11);   // A/B builds (buckets ~ 2^lr_sub)
         a.lr_sub = std::min(std::max(lr_sub, 1), 14);
         if (g->seq_tlimit > 0) a.t_limit = std::min<int64_t>(a.t_limit, g->seq_tlimit);   // HGX_OPT_SEQ_TLIMIT (tests)
         a.nb = nb;
         a.W = W;
         a.maxd = maxd;
-        a.cap = cap;
-        a.tcap = tcap;
-        a.rcap = rcap;
-        a.hflag = hflag_d;
-        PoolScratch w{g, {}};
-        const size_t rows = sizeof(u64) * (size_t)A * (size_t)W;
-        a.vis = (u64*)w.take(rows);
-        a.ctl = (int64_t*)w.take(sizeof(int64_t) * kLsCtlWords);
-        for (int k = 0; k < 2; ++k) {
-            a.fa[k] = (int32_t*)w.take(sizeof(int32_t) * (size_t)std::max<int64_t>(cap, nb));
-            a.fs[k] = (int32_t*)w.take(sizeof(int32_t) * (size_t)std::max<int64_t>(cap, nb));
-        }
-        a.fbase = (int64_t*)w.take(sizeof(int64_t) * (size_t)std::max<int64_t>(cap, nb));
-        a.deg = (int64_t*)w.take(sizeof(int64_t) * (size_t)std::max<int64_t>(cap, nb));
-        a.pre = (int64_t*)w.take(sizeof(int64_t) * (size_t)(std::max<int64_t>(cap, nb) + 1));
-        a.tile = (int64_t*)w.take(sizeof(int64_t) * (size_t)tcap);
-        a.bsum = (int64_t*)w.take(sizeof(int64_t) * kLsG);
-        a.segcap = cap / (2 * kLsDSegs);   // the segments (half of cap), then an overflow region of cap
-        const size_t nd = (size_t)(cap + kLsDSegs * a.segcap);
-        a.disc = (int64_t*)w.take(sizeof(int64_t) * nd);
-        a.dval = (u64*)w.take(sizeof(u64) * nd);
-        a.bcnt = (uint32_t*)w.take(sizeof(uint32_t) * kLrMaxBuckets);
-        a.bcur = (uint32_t*)w.take(sizeof(uint32_t) * kLrMaxBuckets);
-        a.bstart = (int64_t*)w.take(sizeof(int64_t) * (kLrMaxBuckets + 1));
-        a.bk_v = (u64*)w.take(sizeof(u64) * nd);
-        a.bk_sa = (int64_t*)w.take(sizeof(int64_t) * nd);
-        a.pcnt = (uint32_t*)w.take(sizeof(uint32_t) * kLrG * kLrParts);
-        a.pcur = (uint32_t*)w.take(sizeof(uint32_t) * kLrParts);
-        a.out_pair = (int2*)w.take(sizeof(int2) * (size_t)cap);
+        HGX_HIP(hipHostGetDevicePointer((void**)&a.hflag, g->seq_flag, 0));
         // levels of >= pack_min pairs go to the host packed (HGX_OPT_SEQ_PACK_MIN: tests pack tiny levels)
         a.pack_min = g->seq_pack_min > 0 ? g->seq_pack_min : (int64_t)1 << 20;
         a.pack_min = std::max<int64_t>(a.pack_min, 1);
         a.abytes = g->A <= ((int64_t)1 << 24) ? 3 : 4;
-        if (a.pack_min <= cap) {
-            a.patom = (int32_t*)w.take(sizeof(int32_t) * (size_t)cap);
-            a.pclink = (int32_t*)w.take(sizeof(int32_t) * (size_t)cap);
-            a.pwcap = cap / 64 + 2;
-            a.pbcap = cap / kLpBlk + 2;
-            a.pflag = (u64*)w.take(sizeof(u64) * 2 * kLrParts * (size_t)a.pwcap);
-            a.pbb = (uint32_t*)w.take(sizeof(uint32_t) * 2 * kLrParts * (size_t)a.pbcap);
-        } else {
-            a.pack_min = INT64_MAX;   // no level can reach it
-        }
-        a.seedcnt = (uint32_t*)w.take(sizeof(uint32_t) * (size_t)kLsMaxW * 64);
-        a.runs = (int64_t*)w.take(sizeof(int64_t) * 3 * (size_t)rcap);
-        a.hbits = hbits;
-        a.hmask = ((int64_t)1 << hbits) - 1;
-        a.hkey = (u64*)w.take(sizeof(u64) << hbits);
-        a.hval = (u64*)w.take(sizeof(u64) << hbits);
         a.pull = pull_off ? 0 : pull;
         a.I = g->I;
-        a.pin_j = pin_j;
+        a.pin_j = pull ? ensure_pin_j(g) : nullptr;
         a.prof = trace_env("HGX_LS_PROF") ? 1 : 0;
-        if (a.pull && pin_j) {
-            ensure_pull_rec(g, pin_j);
+        if (!a.pull) return;
+        if (a.pin_j) {
+            ensure_pull_rec(g, a.pin_j);
             a.prec = root->pull_rec;
             a.pmeta = root->pull_meta;
         }
+        a.chunks = root->chunks;
+        a.n_chunks = root->n_chunks;
+        a.n_heavy = root->n_heavy;
+        a.heavy_atom = root->heavy_atom;
+    }
+
+    template <class T> T* take(size_t n) { return (T*)w.take(sizeof(T) * n); }
+
+    // The capacities (they start small, grow x4 on overflow and are kept on the graph; HGX_OPT_SEQ_SMALL (tests)
+    // starts them tiny so that every growth path runs) and the scratch buffers they size.
+    void alloc() {
+        const bool small = g->seq_small != 0;
+        cap = std::min(full, std::max<int64_t>(g->ls_cap, small ? 64 : (int64_t)1 << 20));
+        tcap = std::max<int64_t>(g->ls_tcap, small ? 8 : (int64_t)1 << 16);
+        rcap = std::max<int64_t>(g->ls_rcap, small ? 4 : (int64_t)1 << 14);
+        a.hbits = std::max<int>(log2_ceil(std::max<int64_t>(g->ls_hcap, small ? 64 : (int64_t)1 << 21)), 6);
+        a.hmask = ((int64_t)1 << a.hbits) - 1;
+        a.cap = cap;
+        a.tcap = tcap;
+        a.rcap = rcap;
+        n_fr = (size_t)std::max<int64_t>(cap, nb);
+        rows = sizeof(u64) * (size_t)A * (size_t)W;
+        a.vis = (u64*)w.take(rows);
+        a.ctl = take<int64_t>(kLsCtlWords);
+        for (int k = 0; k < 2; ++k) {
+            a.fa[k] = take<int32_t>(n_fr);
+            a.fs[k] = take<int32_t>(n_fr);
+        }
+        a.fbase = take<int64_t>(n_fr);
+        a.deg = take<int64_t>(n_fr);
+        a.pre = take<int64_t>(n_fr + 1);
+        a.tile = take<int64_t>((size_t)tcap);
+        a.bsum = take<int64_t>(kLsG);
+        a.segcap = cap / (2 * kLsDSegs);   // the segments (half of cap), then an overflow region of cap
+        const size_t nd = (size_t)(cap + kLsDSegs * a.segcap);
+        a.disc = take<int64_t>(nd);
+        a.dval = take<u64>(nd);
+        a.bcnt = take<uint32_t>(kLrMaxBuckets);
+        a.bcur = take<uint32_t>(kLrMaxBuckets);
+        a.bstart = take<int64_t>(kLrMaxBuckets + 1);
+        a.bk_v = take<u64>(nd);
+        a.bk_sa = take<int64_t>(nd);
+        a.pcnt = take<uint32_t>(kLrG * kLrParts);
+        a.pcur = take<uint32_t>(kLrParts);
+        a.out_pair = take<int2>((size_t)cap);
+        if (a.pack_min <= cap) {
+            a.patom = take<int32_t>((size_t)cap);
+            a.pclink = take<int32_t>((size_t)cap);
+            a.pwcap = cap / 64 + 2;
+            a.pbcap = cap / kLpBlk + 2;
+            a.pflag = take<u64>(2 * kLrParts * (size_t)a.pwcap);
+            a.pbb = take<uint32_t>(2 * kLrParts * (size_t)a.pbcap);
+        } else {
+            a.pack_min = INT64_MAX;   // no level can reach it
+        }
+        a.seedcnt = take<uint32_t>((size_t)kLsMaxW * 64);
+        a.runs = take<int64_t>(3 * (size_t)rcap);
+        a.hkey = (u64*)w.take(sizeof(u64) << a.hbits);
+        a.hval = (u64*)w.take(sizeof(u64) << a.hbits);
         if (a.pull) {
-            const size_t urows = sizeof(u64) * (size_t)std::max<int64_t>(std::min(cap, A), nb) * (size_t)W;   // |union| <= min(F, A)
+            urows = sizeof(u64) * (size_t)std::max<int64_t>(std::min(cap, A), nb) * (size_t)W;   // |union| <= min(F, A)
             a.frow = (u64*)w.take(urows);
-            a.ubit = (u64*)w.take(sizeof(u64) * (size_t)(A / 64 + 1));
-            a.ulist = (int32_t*)w.take(sizeof(int32_t) * (size_t)std::max<int64_t>(cap, nb));
-            a.uidx = (int32_t*)w.take(sizeof(int32_t) * (size_t)std::max<int64_t>(A, 1));
-            a.ecap = std::min<int64_t>(std::max<int64_t>(cap, nb) * nb, (int64_t)1 << 28);   // <= 1 GB of rows
-            a.E = (uint32_t*)w.take(sizeof(uint32_t) * (size_t)a.ecap);
-            a.chunks = root->chunks;
-            a.n_chunks = root->n_chunks;
-            a.n_heavy = root->n_heavy;
-            a.heavy_atom = root->heavy_atom;
-            a.hbest = (u64*)w.take(sizeof(u64) * (size_t)std::max<int64_t>(root->n_heavy * nb, 1));
+            a.ubit = take<u64>((size_t)(A / 64 + 1));
+            a.ulist = take<int32_t>(n_fr);
+            a.uidx = take<int32_t>((size_t)std::max<int64_t>(A, 1));
+            a.ecap = std::min<int64_t>((int64_t)n_fr * nb, (int64_t)1 << 28);   // <= 1 GB of rows
+            a.E = take<uint32_t>((size_t)a.ecap);
+            a.hbest = take<u64>((size_t)std::max<int64_t>(root->n_heavy * nb, 1));
+        }
+        dseeds = take<int32_t>((size_t)nb);
+    }
+
+    // The examined rows (A x W words: 400 MB for config 2's 64 seeds, where the round-4 key array was
+    // 64 x A x 8 = 25.6 GB) and the push hash start empty; every per-level table is cleared by the level itself.
+    void clear_and_seed() {
+        if (a.pull) {
             HGX_HIP(hipMemsetAsync(a.frow, 0, urows, st));
             HGX_HIP(hipMemsetAsync(a.ubit, 0, sizeof(u64) * (size_t)(A / 64 + 1), st));
             HGX_HIP(hipMemsetAsync(a.hbest, 0xFF, sizeof(u64) * (size_t)std::max<int64_t>(root->n_heavy * nb, 1), st));
         }
-        int32_t* dseeds = (int32_t*)w.take(sizeof(int32_t) * (size_t)nb);
         int32_t* hs = (int32_t*)g->pinned_buf(sizeof(int32_t) * (size_t)nb);
         std::memcpy(hs, seeds, sizeof(int32_t) * (size_t)nb);
         HGX_HIP(hipMemcpyAsync(dseeds, hs, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, st));
-        // the examined rows (A x W words: 400 MB for config 2's 64 seeds, where the round-4 key array
-        // was 64 x A x 8 = 25.6 GB) and the push hash start empty; every per-level table is cleared by
-        // the level itself
         HGX_HIP(hipMemsetAsync(a.vis, 0, rows, st));
-        HGX_HIP(hipMemsetAsync(a.hkey, 0xFF, sizeof(u64) << hbits, st));
-        HGX_HIP(hipMemsetAsync(a.hval, 0xFF, sizeof(u64) << hbits, st));
+        HGX_HIP(hipMemsetAsync(a.hkey, 0xFF, sizeof(u64) << a.hbits, st));
+        HGX_HIP(hipMemsetAsync(a.hval, 0xFF, sizeof(u64) << a.hbits, st));
         HGX_HIP(hipMemsetAsync(a.ctl, 0, sizeof(int64_t) * kLsCtlWords, st));
         hgx_ls_seed<<<grid_for(nb, 256), 256, 0, st>>>(a, nb, dseeds);
         HGX_CHECK_LAUNCH();
-        const u64 base = g->seq_flag_seq;
+        base = g->seq_flag_seq;
+    }
+
+    // Level d's kernels.  Grids: thousands of idle workgroups cost ~10 us a launch on small levels (DESIGN 3.1
+    // item 5); the expand's tiles and the pull's atoms are the work that needs more than a block per CU.
+    void enqueue(int32_t d) {
         static const int lr_scatter_g = ab_int("HGX_LR_SCATTER_G", kLrG);   // A/B builds
         static const int lr_rank_g = ab_int("HGX_LR_RANK_G", kLrG);
         const size_t lp_smem = sizeof(u64) * 4 * (size_t)nb;
-        auto enqueue = [&](int32_t d) {
-            // grids: thousands of idle workgroups cost ~10 us a launch on small levels;
-            // the expand's tiles and the pull's atoms are the work that needs more than a block per CU
-            hgx_ls_degree<<<kLsG, 256, 0, st>>>(a, d);
-            hgx_ls_prefix<<<kLsG, 256, 0, st>>>(a, d);
-            hgx_ls_expand<<<1024, 256, 0, st>>>(a, d);
-            if (a.pull) {
-                hgx_lp_efill<<<512, 256, 0, st>>>(a, d);
-                if (W <= 1) hgx_lp_pull<1><<<2048, 256, lp_smem, st>>>(a, d);
-                else if (W <= 2) hgx_lp_pull<2><<<2048, 256, lp_smem, st>>>(a, d);
-                else if (W <= 4) hgx_lp_pull<4><<<2048, 256, lp_smem, st>>>(a, d);
-                else if (W <= 8) hgx_lp_pull<8><<<2048, 256, lp_smem, st>>>(a, d);
-                else hgx_lp_pull<16><<<2048, 256, lp_smem, st>>>(a, d);
-                hgx_lp_hfinal<<<256, 256, 0, st>>>(a, d);
-            }
-            hgx_lr_count<<<kLrG, 256, 0, st>>>(a, d);
-            hgx_lr_scan<<<1, 1024, 0, st>>>(a, d, base + (u64)d + 1);
-            hgx_lr_split<<<kLrG, 256, 0, st>>>(a, d);   // (the count's block ranges)
-            // the packed parts' run bits / block counts of level d - 2 (same parity) must have reached the host
-            if (d >= 2 && a.pack_min != INT64_MAX) HGX_HIP(hipStreamWaitEvent(st, g->ls_cev[d & 1], 0));
-            for (int q = 0; q < kLrParts; ++q) {
-                hgx_lr_scatter<<<lr_scatter_g, 256, 0, st>>>(a, d, q);
-                hgx_lr_rank<<<lr_rank_g, 256, 0, st>>>(a, d, q);
-                if (a.pack_min != INT64_MAX) {
-                    hgx_lr_pflag<<<kLrG, 256, 0, st>>>(a, d, q);
-                    hgx_lr_pscan<<<1, 1024, 0, st>>>(a, d, q, base + (u64)d + 1);
-                    hgx_lr_pemit<<<kLrG, 256, 0, st>>>(a, d, q);
-                }
-                HGX_HIP(hipEventRecord(g->ls_ev[kLrParts * (d & 1) + q], st));
-            }
-            HGX_CHECK_LAUNCH();
-        };
-        // each level's pairs go to the host on the copy stream as soon as the host has read the level's
-        // size: a host buffer per level, one copy per rank part after that part's event (the last level's
-        // copies overlap its later rank parts and the final runs pass)
-        struct LevelPart {   // a packed level's rank part in the level buffer
-            int64_t b, e;
-            const int32_t* link;
-            const u64* flags;
-            const uint32_t* bb;
-            hipEvent_t ready;
-        };
-        struct LevelBuf {
-            PoolBuf b;
-            int64_t out0, n;
-            bool packed = false;
-            std::vector<LevelPart> parts;
-            int ab = 4;                   // (packed) bytes an atom
-            hipEvent_t ready = nullptr;   // (unpacked: after all its copies)
-        };
-        // the pair copies complete after the call returns (the readers wait per segment): an event after
-        // each copy group, owned by the result
-        std::vector<hipEvent_t> cevs;
-        struct EvGuard {   // an attempt that fails drops its events
-            std::vector<hipEvent_t>* v;
-            bool keep = false;
-            ~EvGuard() {
-                if (keep) return;
-                for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-                v->clear();
-            }
-        } ev_guard{&cevs};
-        auto new_copy_event = [&](hipStream_t on) {
-            hipEvent_t e = nullptr;
-            HGX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            cevs.push_back(e);
-            HGX_HIP(hipEventRecord(e, on));
-            return e;
-        };
-        std::vector<LevelBuf> lbufs;
-        struct GiveBack {   // an attempt that fails returns its level buffers after the copies drained
-            hgx_graph* g;
-            hipStream_t cs;
-            std::vector<LevelBuf>* v;
-            bool keep = false;
-            ~GiveBack() {
-                if (keep || v->empty()) return;
-                (void)hipStreamSynchronize(cs);
-                std::lock_guard<std::mutex> lk(g->seq_mu);
-                for (auto& x : *v) g->seq_hbufs.push_back(x.b);
-            }
-        } give_back{g, cs, &lbufs};
-        auto copy_level = [&](int32_t d, int64_t out0, int64_t n) {
-            const u64* bnd = g->seq_flag + 8 + (kLrParts + 1) * (d & 1);
-            if (n < a.pack_min) {
-                PoolBuf hb = take_host_buf(g, 8 * (size_t)n);   // (link, atom) interleaved
-                lbufs.push_back({hb, out0, n});
-                int2* hp = (int2*)hb.p;
-                for (int q = 0; q < kLrParts; ++q) {
-                    const int64_t b = (int64_t)bnd[q], e = (int64_t)bnd[q + 1];
-                    if (b < 0 || e > n || e < b) fail(HGX_E_DEVICE, "hgx_bfs_sequence: rank-part bounds inconsistent");
-                    if (e == b) continue;
-                    HGX_HIP(hipStreamWaitEvent(cs, g->ls_ev[kLrParts * (d & 1) + q], 0));
-                    HGX_HIP(hipMemcpyAsync(hp + b, a.out_pair + out0 + b, sizeof(int2) * (size_t)(e - b),
-                                           hipMemcpyDeviceToHost, cs));
-                }
-                HGX_HIP(hipEventRecord(g->ls_cev[d & 1], cs));
-                lbufs.back().ready = new_copy_event(cs);
-                return;
-            }
-            // packed: atoms [n] (abytes each) | run links [n] | run-start words [n / 64 + kLrParts + 1] | block counts
-            const int ab = a.abytes;
-            const size_t nw = (size_t)(n / 64 + kLrParts + 1), nbb = (size_t)(n / kLpBlk + kLrParts + 1);
-            const size_t areg = ((size_t)ab * (size_t)n + 7) & ~(size_t)7;
-            PoolBuf hb = take_host_buf(g, areg + 4 * (size_t)n + 8 * nw + 4 * nbb);
-            LevelBuf lb{hb, out0, n, true, {}};
-            lb.ab = ab;
-            char* h_atom = (char*)hb.p;
-            int32_t* h_link = (int32_t*)(h_atom + areg);
-            u64* h_flag = (u64*)(h_link + n);
-            uint32_t* h_bb = (uint32_t*)(h_flag + nw);
-            for (int q = 0; q < kLrParts; ++q) {
-                const int64_t b = (int64_t)bnd[q], e = (int64_t)bnd[q + 1];
-                if (b < 0 || e > n || e < b) fail(HGX_E_DEVICE, "hgx_bfs_sequence: rank-part bounds inconsistent");
-                if (e == b) continue;
-                const u64* hp = g->seq_flag + kPackWords + 2 * ((d & 1) * kLrParts + q);
-                wait_host_word(hp + 1, base + (u64)d + 1, st, "hgx_bfs_sequence: a packed part's run count never arrived");
-                const int64_t runs = (int64_t)__atomic_load_n(hp, __ATOMIC_RELAXED);
-                const int64_t np = e - b, pw = (np + 63) / 64, pbk = (np + kLpBlk - 1) / kLpBlk;
-                if (runs < 1 || runs > np) fail(HGX_E_DEVICE, "hgx_bfs_sequence: packed part inconsistent");
-                // a part's words / block counts start after the earlier parts' (b / 64 + q >= their end)
-                u64* hf = h_flag + b / 64 + q;
-                uint32_t* hbk = h_bb + b / kLpBlk + q;
-                const hipStream_t c = (q & 1) ? cs2 : cs;
-                const int64_t slot = (int64_t)(d & 1) * kLrParts + q;
-                HGX_HIP(hipStreamWaitEvent(c, g->ls_ev[kLrParts * (d & 1) + q], 0));
-                // the copies start at a 64-byte boundary of the level (out0 + b0): the extra leading atoms are
-                // the previous part's, already final (same values), the extra leading links fall in the previous
-                // part's link area past its runs or are its own final values
-                const int64_t al = ab == 4 ? 16 : 64;   // pairs a 64-byte boundary of the atoms spans
-                const int64_t b0 = std::max<int64_t>(0, ((out0 + b) & ~(al - 1)) - out0);
-                static const bool align = ab_int("HGX_LS_PACK_ALIGN", 1) != 0;   // A/B builds
-                const int64_t bc = align ? b0 : b;
-                HGX_HIP(hipMemcpyAsync(h_atom + (size_t)ab * bc, (const char*)a.patom + (size_t)ab * (out0 + bc),
-                                       (size_t)ab * (size_t)(e - bc), hipMemcpyDeviceToHost, c));
-                HGX_HIP(hipMemcpyAsync(h_link + bc, a.pclink + out0 + bc, sizeof(int32_t) * (size_t)(b + runs - bc),
-                                       hipMemcpyDeviceToHost, c));
-                HGX_HIP(hipMemcpyAsync(hf, a.pflag + slot * a.pwcap, sizeof(u64) * (size_t)pw, hipMemcpyDeviceToHost, c));
-                HGX_HIP(hipMemcpyAsync(hbk, a.pbb + slot * a.pbcap, sizeof(uint32_t) * (size_t)pbk, hipMemcpyDeviceToHost, c));
-                lb.parts.push_back({b, e, h_link + b, hf, hbk, new_copy_event(c)});
-            }
-            if (cs2 != cs) HGX_HIP(hipStreamWaitEvent(cs, new_copy_event(cs2), 0));   // the level's copies joined on cs
-            HGX_HIP(hipEventRecord(g->ls_cev[d & 1], cs));
-            new_copy_event(cs);   // (the last event of the call: covers both copy streams)
-            lbufs.push_back(std::move(lb));
-        };
-        int64_t total = 0, status = 0;
-        int32_t dw = 0, enq = 0;
-        if (maxd > 0) {
-            enqueue(0);
-            enq = 1;
+        hgx_ls_degree<<<kLsG, 256, 0, st>>>(a, d);
+        hgx_ls_prefix<<<kLsG, 256, 0, st>>>(a, d);
+        hgx_ls_expand<<<1024, 256, 0, st>>>(a, d);
+        if (a.pull) {
+            hgx_lp_efill<<<512, 256, 0, st>>>(a, d);
+            if (W <= 1) hgx_lp_pull<1><<<2048, 256, lp_smem, st>>>(a, d);
+            else if (W <= 2) hgx_lp_pull<2><<<2048, 256, lp_smem, st>>>(a, d);
+            else if (W <= 4) hgx_lp_pull<4><<<2048, 256, lp_smem, st>>>(a, d);
+            else if (W <= 8) hgx_lp_pull<8><<<2048, 256, lp_smem, st>>>(a, d);
+            else hgx_lp_pull<16><<<2048, 256, lp_smem, st>>>(a, d);
+            hgx_lp_hfinal<<<256, 256, 0, st>>>(a, d);
         }
+        hgx_lr_count<<<kLrG, 256, 0, st>>>(a, d);
+        hgx_lr_scan<<<1, 1024, 0, st>>>(a, d, base + (u64)d + 1);
+        hgx_lr_split<<<kLrG, 256, 0, st>>>(a, d);   // (the count's block ranges)
+        // the packed parts' run bits / block counts of level d - 2 (same parity) must have reached the host
+        if (d >= 2 && a.pack_min != INT64_MAX) HGX_HIP(hipStreamWaitEvent(st, g->ls_cev[d & 1], 0));
+        for (int q = 0; q < kLrParts; ++q) {
+            hgx_lr_scatter<<<lr_scatter_g, 256, 0, st>>>(a, d, q);
+            hgx_lr_rank<<<lr_rank_g, 256, 0, st>>>(a, d, q);
+            if (a.pack_min != INT64_MAX) {
+                hgx_lr_pflag<<<kLrG, 256, 0, st>>>(a, d, q);
+                hgx_lr_pscan<<<1, 1024, 0, st>>>(a, d, q, base + (u64)d + 1);
+                hgx_lr_pemit<<<kLrG, 256, 0, st>>>(a, d, q);
+            }
+            HGX_HIP(hipEventRecord(g->ls_ev[kLrParts * (d & 1) + q], st));
+        }
+        HGX_CHECK_LAUNCH();
+    }
+
+    hipEvent_t new_copy_event(hipStream_t on) {
+        hipEvent_t e = nullptr;
+        HGX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        cevs.push_back(e);
+        HGX_HIP(hipEventRecord(e, on));
+        return e;
+    }
+
+    // Rank part q's pairs [b, e) of level d (n pairs), from the bounds the scan kernel left; false: none.
+    bool part_range(int32_t d, int q, int64_t n, int64_t* b, int64_t* e) const {
+        const u64* bnd = g->seq_flag + 8 + (kLrParts + 1) * (d & 1);
+        *b = (int64_t)bnd[q];
+        *e = (int64_t)bnd[q + 1];
+        if (*b < 0 || *e > n || *e < *b) fail(HGX_E_DEVICE, "hgx_bfs_sequence: rank-part bounds inconsistent");
+        return *e > *b;
+    }
+
+    // Level d's n pairs (from out0 of the chunk's pairs) as interleaved (link, atom).
+    void copy_level_plain(int32_t d, int64_t out0, int64_t n) {
+        PoolBuf hb = take_host_buf(g, 8 * (size_t)n);
+        lbufs.push_back({hb, out0, n});
+        int2* hp = (int2*)hb.p;
+        for (int q = 0; q < kLrParts; ++q) {
+            int64_t b, e;
+            if (!part_range(d, q, n, &b, &e)) continue;
+            HGX_HIP(hipStreamWaitEvent(cs, g->ls_ev[kLrParts * (d & 1) + q], 0));
+            HGX_HIP(hipMemcpyAsync(hp + b, a.out_pair + out0 + b, sizeof(int2) * (size_t)(e - b), hipMemcpyDeviceToHost, cs));
+        }
+        HGX_HIP(hipEventRecord(g->ls_cev[d & 1], cs));
+        lbufs.back().ready = new_copy_event(cs);
+    }
+
+    // Level d's n pairs packed: atoms [n] (abytes each) | run links [n] | run-start words [n / 64 + kLrParts + 1] |
+    // block counts.
+    void copy_level_packed(int32_t d, int64_t out0, int64_t n) {
+        const int ab = a.abytes;
+        const size_t nw = (size_t)(n / 64 + kLrParts + 1), nbb = (size_t)(n / kLpBlk + kLrParts + 1);
+        const size_t areg = ((size_t)ab * (size_t)n + 7) & ~(size_t)7;
+        PoolBuf hb = take_host_buf(g, areg + 4 * (size_t)n + 8 * nw + 4 * nbb);
+        lbufs.push_back({hb, out0, n, true, {}});   // (in the list at once: a failure below returns it with the others)
+        lbufs.back().ab = ab;
+        char* h_atom = (char*)hb.p;
+        int32_t* h_link = (int32_t*)(h_atom + areg);
+        u64* h_flag = (u64*)(h_link + n);
+        uint32_t* h_bb = (uint32_t*)(h_flag + nw);
+        for (int q = 0; q < kLrParts; ++q) {
+            int64_t b, e;
+            if (!part_range(d, q, n, &b, &e)) continue;
+            const u64* hp = g->seq_flag + kPackWords + 2 * ((d & 1) * kLrParts + q);
+            wait_host_word(hp + 1, base + (u64)d + 1, st, "hgx_bfs_sequence: a packed part's run count never arrived");
+            const int64_t runs = (int64_t)__atomic_load_n(hp, __ATOMIC_RELAXED);
+            const int64_t np = e - b, pw = (np + 63) / 64, pbk = (np + kLpBlk - 1) / kLpBlk;
+            if (runs < 1 || runs > np) fail(HGX_E_DEVICE, "hgx_bfs_sequence: packed part inconsistent");
+            // a part's words / block counts start after the earlier parts' (b / 64 + q >= their end)
+            u64* hf = h_flag + b / 64 + q;
+            uint32_t* hbk = h_bb + b / kLpBlk + q;
+            const hipStream_t c = (q & 1) ? cs2 : cs;
+            const int64_t slot = (int64_t)(d & 1) * kLrParts + q;
+            HGX_HIP(hipStreamWaitEvent(c, g->ls_ev[kLrParts * (d & 1) + q], 0));
+            // the copies start at a 64-byte boundary of the level (out0 + b0): the extra leading atoms are
+            // the previous part's, already final (same values), the extra leading links fall in the previous
+            // part's link area past its runs or are its own final values
+            const int64_t al = ab == 4 ? 16 : 64;   // pairs a 64-byte boundary of the atoms spans
+            const int64_t b0 = std::max<int64_t>(0, ((out0 + b) & ~(al - 1)) - out0);
+            static const bool align = ab_int("HGX_LS_PACK_ALIGN", 1) != 0;   // A/B builds
+            const int64_t bc = align ? b0 : b;
+            HGX_HIP(hipMemcpyAsync(h_atom + (size_t)ab * bc, (const char*)a.patom + (size_t)ab * (out0 + bc),
+                                   (size_t)ab * (size_t)(e - bc), hipMemcpyDeviceToHost, c));
+            HGX_HIP(hipMemcpyAsync(h_link + bc, a.pclink + out0 + bc, sizeof(int32_t) * (size_t)(b + runs - bc),
+                                   hipMemcpyDeviceToHost, c));
+            HGX_HIP(hipMemcpyAsync(hf, a.pflag + slot * a.pwcap, sizeof(u64) * (size_t)pw, hipMemcpyDeviceToHost, c));
+            HGX_HIP(hipMemcpyAsync(hbk, a.pbb + slot * a.pbcap, sizeof(uint32_t) * (size_t)pbk, hipMemcpyDeviceToHost, c));
+            lbufs.back().parts.push_back({b, e, h_link + b, hf, hbk, new_copy_event(c)});
+        }
+        if (cs2 != cs) HGX_HIP(hipStreamWaitEvent(cs, new_copy_event(cs2), 0));   // the level's copies joined on cs
+        HGX_HIP(hipEventRecord(g->ls_cev[d & 1], cs));
+        new_copy_event(cs);   // (the last event of the call: covers both copy streams)
+    }
+
+    // Runs the levels, the kernels one level ahead of the host, which reads each level's size and starts its
+    // copy; then the control words.  The status: 0, or LsStatus bits.
+    int64_t drain() {
+        int64_t status = 0;
+        int32_t dw = 0, enq = 0;
+        if (maxd > 0) enqueue(enq++);
         while (dw < enq) {
-            if (enq < maxd && enq == dw + 1) enqueue(enq++);   // one level ahead of the host
+            if (enq < maxd && enq == dw + 1) enqueue(enq++);
             const u64 want = base + (u64)dw + 1;
             const u64* hf = g->seq_flag + 4 * (dw & 1);
             wait_host_word(hf + 2, want, st, "hgx_bfs_sequence: a level's size never arrived");
@@ -4843,33 +4968,38 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
             status = (int64_t)__atomic_load_n(hf + 1, __ATOMIC_RELAXED);
             if (status) break;
             seq_mark("level size read");
-            if (n > 0) copy_level(dw, total, n);
+            if (n > 0 && n < a.pack_min) copy_level_plain(dw, total, n);
+            else if (n > 0) copy_level_packed(dw, total, n);
             total += n;
             ++dw;
             if (n == 0) break;
         }
         g->seq_flag_seq = base + (u64)enq + 2;
         seq_mark("levels read");
-        std::vector<int64_t> ctl(kLsCtlWords);
+        ctl.resize(kLsCtlWords);
         HGX_HIP(hipMemcpyAsync(ctl.data(), a.ctl, sizeof(int64_t) * kLsCtlWords, hipMemcpyDeviceToHost, st));
         spin_sync(st);
-        status |= ctl[kLsStatus];
-        if (status) {
-            if (status & 16) return false;   // 32-bit level keys do not fit: the caller splits the chunk
-            // each attempt stops at the first level that overflows, so a tiny start (HGX_LS_SMALL) may need
-            // one attempt per capacity and level; the default starts converge in a few
-            if (attempt > 48) fail(HGX_E_DEVICE, "hgx_bfs_sequence: level-synchronous capacities did not converge");
-            if (status & 1) g->ls_cap = std::min(full, cap * 4);
-            if (status & 2) g->ls_rcap = rcap * 4;
-            if (status & 8) g->ls_tcap = tcap * 4;
-            if (status & 32) g->ls_hcap = ((int64_t)1 << hbits) * 4;
-            if (status & 128) pull_off = true;   // a pull pass's hit list overflowed: this call pushes
-            continue;   // rerun the chunk with the grown capacities (kept on the graph)
-        }
-        const int64_t nruns = ctl[kLsRuns];
-        give_back.keep = true;
+        return status | ctl[kLsStatus];
+    }
+
+    // After a status: the chunk is split (32-bit level keys do not fit), or the short capacities grow on the graph
+    // and the chunk runs again.  Each attempt stops at the first level that overflows, so a tiny start
+    // (HGX_OPT_SEQ_SMALL) may need one attempt per capacity and level; the default starts converge in a few.
+    Next grow(int64_t status, int attempt, bool* pull_off) const {
+        if (status & kLsKeysWide) return Next::kSplit;
+        if (attempt > 48) fail(HGX_E_DEVICE, "hgx_bfs_sequence: level-synchronous capacities did not converge");
+        if (status & kLsDiscFull) g->ls_cap = std::min(full, cap * 4);
+        if (status & kLsRunsFull) g->ls_rcap = rcap * 4;
+        if (status & kLsTilesFull) g->ls_tcap = tcap * 4;
+        if (status & kLsHashFull) g->ls_hcap = ((int64_t)1 << a.hbits) * 4;
+        if (status & kLsPullHitsFull) *pull_off = true;   // this call pushes
+        return Next::kRetry;
+    }
+
+    // The attempt succeeded: its level buffers, copy events and counters go to the result.
+    void keep(SeqOut& out) {
+        kept = true;
         for (auto& x : lbufs) out.bufs.push_back(x.b);
-        ev_guard.keep = true;
         for (hipEvent_t e : cevs) out.evs.push_back(e);
         out.traversed += (double)ctl[kLsTrav];
         out.bytes += (double)ctl[kLsBytes];
@@ -4880,7 +5010,32 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
                          ctl[kLsProf] * 1e-5, ctl[kLsProf + 1] * 1e-5, ctl[kLsProf + 2] * 1e-5, ctl[kLsProf + 6] * 1e-5,
                          ctl[kLsProf + 7] * 1e-5, (long long)ctl[kLsProf + 3], (long long)ctl[kLsProf + 4],
                          (long long)ctl[kLsProf + 5]);
-        // the runs (3 x nruns); the pairs are in the level buffers once the copy stream drained
+    }
+
+    // A run [b, e) of pairs -> its segments in the level buffer (levels are consecutive ranges of [0, total); a
+    // packed level's run may cross rank parts: a segment per part).
+    void run_segs(int64_t b, int64_t e, int32_t dist, std::vector<Seg>& out_segs) const {
+        size_t L = 0;
+        while (L + 1 < lbufs.size() && lbufs[L + 1].out0 <= b) ++L;
+        const LevelBuf& lb = lbufs[L];
+        if (!lb.packed) {
+            out_segs.push_back(Seg::interleaved((const int32_t*)lb.b.p + 2 * (b - lb.out0), e - b, dist, lb.ready));
+            return;
+        }
+        const int64_t rb = b - lb.out0, re = e - lb.out0;
+        const char* h_atom = (const char*)lb.b.p;
+        for (const LevelPart& pt : lb.parts) {
+            const int64_t lo = std::max(rb, pt.b), hi = std::min(re, pt.e);
+            if (hi <= lo) continue;
+            out_segs.push_back(Seg::packed(pt.link, pt.flags, pt.bb, lo - pt.b, h_atom + (size_t)lb.ab * lo, lb.ab, hi - lo,
+                                           dist, pt.ready));
+        }
+    }
+
+    // The runs (3 x nruns: distance, seed, first pair) -> per seed its segments in distance order; the pairs are
+    // in the level buffers once the copy streams drained.
+    void assemble(SeqOut& out, int64_t seed0) {
+        const int64_t nruns = ctl[kLsRuns];
         PoolBuf hb = take_host_buf(g, 24 * (size_t)std::max<int64_t>(nruns, 1));
         out.bufs.push_back(hb);
         int64_t* hr = (int64_t*)hb.p;
@@ -4890,41 +5045,14 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
         // the copies run on: later work on this stream (the scratch buffers' next users) waits for them, the
         // readers wait per segment (Seg::ready), the result's free waits for all of them
         if (!cevs.empty()) HGX_HIP(hipStreamWaitEvent(st, cevs.back(), 0));
-        // a run [b, e) of pairs -> its segments in the level buffer (levels are consecutive ranges of
-        // [0, total); a packed level's run may cross rank parts: a segment per part)
-        auto run_segs = [&](int64_t b, int64_t e, int32_t dist, std::vector<Seg>& out_segs) {
-            size_t L = 0;
-            while (L + 1 < lbufs.size() && lbufs[L + 1].out0 <= b) ++L;
-            const LevelBuf& lb = lbufs[L];
-            if (!lb.packed) {
-                const int32_t* pl = (const int32_t*)lb.b.p + 2 * (b - lb.out0);
-                Seg sg{pl, pl + 1, nullptr, e - b, dist, 2};
-                sg.ready = lb.ready;
-                out_segs.push_back(sg);
-                return;
-            }
-            const int64_t rb = b - lb.out0, re = e - lb.out0;
-            const char* h_atom = (const char*)lb.b.p;
-            for (const LevelPart& pt : lb.parts) {
-                const int64_t lo = std::max(rb, pt.b), hi = std::min(re, pt.e);
-                if (hi <= lo) continue;
-                Seg sg{pt.link, (const int32_t*)(h_atom + (size_t)lb.ab * lo), nullptr, hi - lo, dist, 0};
-                sg.ab = lb.ab;
-                sg.flags = pt.flags;
-                sg.bb = pt.bb;
-                sg.pi = lo - pt.b;
-                sg.ready = pt.ready;
-                out_segs.push_back(sg);
-            }
-        };
         // runs partition [0, total) in pair order; each seed's runs in distance order are its pairs
         std::vector<int64_t> ord((size_t)nruns);
         for (int64_t k = 0; k < nruns; ++k) ord[k] = k;
         std::sort(ord.begin(), ord.end(), [&](int64_t x, int64_t y) { return hr[3 * x + 2] < hr[3 * y + 2]; });
+        auto run_end = [&](int64_t k) { return k + 1 < nruns ? hr[3 * ord[k + 1] + 2] : total; };
         // the runs must tile [0, total) exactly (one per seed and level with pairs)
         for (int64_t k = 0; k < nruns; ++k) {
-            const int64_t b = hr[3 * ord[k] + 2], e = k + 1 < nruns ? hr[3 * ord[k + 1] + 2] : total;
-            const int64_t sd = hr[3 * ord[k] + 1];
+            const int64_t b = hr[3 * ord[k] + 2], e = run_end(k), sd = hr[3 * ord[k] + 1];
             if ((k == 0 && b != 0) || e <= b || sd < 0 || sd >= nb)
                 fail(HGX_E_DEVICE, "hgx_bfs_sequence: level engine runs inconsistent (run " + std::to_string(k) + " of " +
                                        std::to_string(nruns) + ": start " + std::to_string(b) + " end " +
@@ -4938,13 +5066,30 @@ bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t m
         for (int32_t s = 0; s < nb; ++s) {
             std::sort(per[s].begin(), per[s].end());
             for (auto& dk : per[s]) {
-                const int64_t k = dk.second, b = hr[3 * ord[k] + 2];
-                const int64_t e = k + 1 < nruns ? hr[3 * ord[k + 1] + 2] : total;
-                run_segs(b, e, (int32_t)dk.first, out.segs[(size_t)(seed0 + s)]);
+                run_segs(hr[3 * ord[dk.second] + 2], run_end(dk.second), (int32_t)dk.first, out.segs[(size_t)(seed0 + s)]);
                 out.deepest = std::max(out.deepest, (int32_t)dk.first);
             }
         }
-        return true;
+    }
+};
+
+// The level-synchronous engine over a chunk of <= 1024 seeds; false when a level's keys do not fit 32 bits (the
+// caller splits the chunk).  A capacity that was short has grown on the graph: the chunk runs again.
+bool seq_levels2_chunk(hgx_graph* g, const int32_t* seeds, int32_t nb, int32_t maxd, const hgx_algen_opts& o,
+                       SeqOut& out, int64_t seed0) {
+    bool pull_off = false;
+    for (int attempt = 0;; ++attempt) {
+        LevelChunk c(g, seeds, nb, maxd);
+        c.bind(o, pull_off);
+        c.alloc();
+        c.clear_and_seed();
+        const int64_t status = c.drain();
+        if (!status) {
+            c.keep(out);
+            c.assemble(out, seed0);
+            return true;
+        }
+        if (c.grow(status, attempt, &pull_off) == LevelChunk::Next::kSplit) return false;
     }
 }
 
@@ -4990,27 +5135,48 @@ void seq_levels_all(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t
 // ---- the multi-workgroup stage, host side ----
 
 
-// Whether the grid fits: every workgroup must be resident at once (the barrier waits for all), at most
-// 2 per CU and one CU slot left for other streams' kernels.
 int co_threads() {
     static const int v = ab_int("HGX_CO_THREADS", 0) == 512 ? 512 : kCoThreads;
     return v;
 }
 
+// The grid of a persistent kernel whose workgroups wait for each other: every workgroup must be resident at
+// once (the barrier waits for all), at most 2 per CU and one CU slot left for other streams' kernels.  0: does
+// not fit.  cap_env: the A/B builds' HGX_CO_BLOCKS / HGX_SC_BLOCKS.
+template <class Kernel>
+int32_t resident_grid(hgx_graph* g, Kernel kernel, int threads, int cap_env) {
+    int per_cu = 0, cus = 0;
+    HGX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0));
+    HGX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
+    const int64_t blocks = (int64_t)std::min(per_cu - 1, 2) * cus;
+    const int64_t cap = cap_env >= kCoMinBlocks ? std::min(cap_env, kCoMaxBlocks) : kCoBlocks;
+    return blocks >= kCoMinBlocks ? (int32_t)std::min<int64_t>(blocks, cap) : 0;
+}
 
 bool co_fits(hgx_graph* g) {
     if (g->co_ok < 0) {
-        int per_cu = 0, cus = 0;
-        const int nt = co_threads();
-        if (nt == 512) HGX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hgx_bfs_coop<512>, 512, 0));
-        else HGX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hgx_bfs_coop<kCoThreads>, kCoThreads, 0));
-        HGX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
-        const int64_t blocks = (int64_t)std::min(per_cu - 1, 2) * cus;
-        static const int cap_env = ab_int("HGX_CO_BLOCKS", 0);   // A/B builds
-        const int64_t cap = cap_env >= kCoMinBlocks ? std::min(cap_env, kCoMaxBlocks) : kCoBlocks;
-        g->co_ok = blocks >= kCoMinBlocks ? (int32_t)std::min<int64_t>(blocks, cap) : 0;
+        static const int cap_env = ab_int("HGX_CO_BLOCKS", 0);
+        g->co_ok = co_threads() == 512 ? resident_grid(g, hgx_bfs_coop<512>, 512, cap_env)
+                                       : resident_grid(g, hgx_bfs_coop<kCoThreads>, kCoThreads, cap_env);
     }
     return g->co_ok > 0;
+}
+
+// The grid stages' per-seed visited bitmaps (hgx_graph::co_vis, shared by hgx_bfs_coop and hgx_seq_coop): zero
+// between launches (a clean launch clears the bits it set), grown to the seed count.
+void ensure_co_vis(hgx_graph* g, int64_t n_seeds) {
+    if (g->co_vis_seeds >= n_seeds) return;
+    const size_t bytes = sizeof(u64) * (size_t)(n_seeds * (g->A / 64 + 1));
+    if (g->co_vis) HGX_HIP(hipFree(g->co_vis));
+    g->co_vis = nullptr;
+    g->co_vis_seeds = 0;
+    HGX_HIP(hipMalloc(&g->co_vis, bytes));
+    HGX_HIP(hipMemsetAsync(g->co_vis, 0, bytes, g->stream));
+    g->co_vis_seeds = n_seeds;
+}
+// After a launch that did not finish: the bitmaps may hold bits of atoms no pair records, so they are cleared whole.
+void clear_co_vis(hgx_graph* g) {
+    HGX_HIP(hipMemsetAsync(g->co_vis, 0, sizeof(u64) * (size_t)(g->co_vis_seeds * (g->A / 64 + 1)), g->stream));
 }
 
 // One launch of the grid stage: its scratch, pair list and mapped readout, returned to the graph's
@@ -5022,9 +5188,6 @@ struct CoRun {
     int2* pairs = nullptr;
     int64_t pcap = 0;
     PoolBuf hb{nullptr, 0};
-    int64_t* hm = nullptr;                  // the mapped readout (CoArgs::hmeta)
-    size_t m_seg = 0, m_sel = 0, m_lev = 0;  // its pairs-per-segment, batch-index and level-count parts
-    size_t m_blk = 0;                        //   and the blocks' algorithmic bytes
     explicit CoRun(hgx_graph* gg) : g(gg), sc{gg, {}} {}
     CoRun(const CoRun&) = delete;
     CoRun& operator=(const CoRun&) = delete;
@@ -5035,172 +5198,171 @@ struct CoRun {
             g->seq_hbufs.push_back(hb);
         }
     }
-};
 
-// Buffers and arguments of a launch over k seeds (k = -1: the workgroup stage's hand-over, up to kcap
-// seeds); the control words are cleared on the stream.
-void co_setup(hgx_graph* g, CoRun& r, int32_t k, int32_t kcap, int32_t max_depth, const hgx_algen_opts& o) {
-    hipStream_t st = g->stream;
-    const int mode = mode_of(o);
-    const int64_t vwords = g->A / 64 + 1;
-    if (g->co_vis_seeds < kcap) {   // zero-invariant bitmaps, grown to the seed count
-        if (g->co_vis) HGX_HIP(hipFree(g->co_vis));
-        g->co_vis = nullptr;
-        g->co_vis_seeds = 0;
-        const int64_t want = std::max<int64_t>(kcap, 8);
-        HGX_HIP(hipMalloc(&g->co_vis, sizeof(u64) * (size_t)(want * vwords)));
-        HGX_HIP(hipMemsetAsync(g->co_vis, 0, sizeof(u64) * (size_t)(want * vwords), st));
-        g->co_vis_seeds = want;
+    // The mapped readout (CoArgs::hmeta), kcap = a.kcap: [0] status (-1 until block 0 leaves the level loop
+    // normally), [1] levels, [2] seeds (chained: the kernel writes how many it took), [3] set by any block that
+    // timed out on a grid barrier, [4 + 2 j] {pairs, traversed} of seed j | pairs per segment [kCoSegs] | the seeds'
+    // batch indices [kcap] | per seed the pairs before the end of each level [kcap][kCoMaxLevels] | trace
+    // [2][kCoMaxLevels] | the blocks' algorithmic bytes [kCoMaxBlocks]
+    int64_t* hm = nullptr;
+    size_t m_seg() const { return 4 + 2 * (size_t)a.kcap; }
+    size_t m_sel() const { return m_seg() + kCoSegs; }
+    size_t m_lev() const { return m_sel() + (size_t)a.kcap; }
+    size_t m_blk() const { return m_lev() + (size_t)(a.kcap + 2) * kCoMaxLevels; }
+    int64_t status() const { return hm[0]; }
+    int32_t n_levels() const { return (int32_t)hm[1]; }
+    int64_t seeds_taken() const { return hm[2]; }
+    bool timed_out() const { return hm[3] != 0; }
+    int64_t pairs_of(int32_t j) const { return hm[4 + 2 * j]; }
+    int64_t traversed_of(int32_t j) const { return hm[5 + 2 * j]; }
+    const int64_t* seg_pairs() const { return hm + m_seg(); }
+    const int64_t* batch_indices() const { return hm + m_sel(); }   // of the chained launch's seeds, the slots' order
+    const int64_t* level_ends(int32_t j) const { return hm + m_lev() + (size_t)j * kCoMaxLevels; }
+    const int64_t* level_trace() const { return level_ends(a.kcap); }
+    double block_bytes() const {
+        double bytes = 0;
+        for (int b = 0; b < g->co_ok; ++b) bytes += (double)hm[m_blk() + b];
+        return bytes;
     }
-    if (g->co_pcap == 0) g->co_pcap = (int64_t)1 << 22;
-    if (g->co_fr == 0) g->co_fr = (int64_t)1 << 21;
-    const int64_t fr_seg = g->co_fr / kCoSegs;   // work items per segment and level
-    r.pcap = g->co_pcap;
-    int4* fr = (int4*)r.sc.take(sizeof(int4) * 3 * kCoSegs * (size_t)fr_seg);
-    r.pairs = (int2*)g->alloc(sizeof(int2) * (size_t)r.pcap);
-    const size_t ctl_words = kCoCtlWords + 2 * (size_t)kcap;
-    const size_t ctl_bytes = sizeof(u64) * ctl_words + 2 * sizeof(int32_t) * (size_t)kcap;
-    u64* ctl = (u64*)r.sc.take(ctl_bytes);
-    int32_t* sel_idx = (int32_t*)(ctl + ctl_words);
-    HGX_HIP(hipMemsetAsync(ctl, 0, ctl_bytes, st));
-    r.m_seg = 4 + 2 * (size_t)kcap;
-    r.m_sel = r.m_seg + kCoSegs;
-    r.m_lev = r.m_sel + (size_t)kcap;
-    r.m_blk = r.m_lev + (size_t)(kcap + 2) * kCoMaxLevels;
-    r.hb = take_host_buf(g, sizeof(int64_t) * (r.m_blk + kCoMaxBlocks));
-    r.hm = (int64_t*)r.hb.p;
-    r.hm[0] = -1;   // written once, at the normal exit of block 0
-    r.hm[1] = 0;
-    r.hm[2] = k;
-    r.hm[3] = 0;    // set by any block that timed out on a grid barrier
-    void* hmd = nullptr;
-    HGX_HIP(hipHostGetDevicePointer(&hmd, r.hm, 0));
-    CoArgs& a = r.a;
-    a.k = k;
-    a.kcap = kcap;
-    a.sel_idx = sel_idx;
-    a.seeds = sel_idx + kcap;
-    a.inc_off = g->inc_off;
-    a.inc_row = g->inc_row;
-    a.inc_type = g->inc_type;
-    a.yf = mode != kSym ? g->inc_yf : nullptr;
-    stage_items(g, mode, o, a);
-    a.tgt_off = g->tgt_off;
-    a.tgt_idx = g->tgt_idx;
-    a.want_type = o.link_type;
-    a.min_arity = o.return_source ? 1 : 2;
-    a.mode = mode;
-    a.maxd = max_depth < 0 ? INT32_MAX : max_depth;
-    static const int chunk_env = ab_int("HGX_CO_CHUNK", 0);
-    a.chunk = chunk_env > 0 ? std::min(chunk_env, 1 << 20) : kCoChunk;   // entries < 2^23 (co_item)
-    static const int bg_env = ab_int("HGX_CO_BARGROUPS", 0);   // A/B builds
-    a.bgroups = bg_env > 0 ? std::min(bg_env, kCoBarGroups) : 1;
-    static const bool lite_off = ab_int("HGX_CO_LITE", 1) == 0;   // A/B builds
-    a.lite = lite_off ? 0 : 1;
-    a.vwords = vwords;
-    a.vis = g->co_vis;
-    a.fr = fr;
-    a.fr_seg = fr_seg;
-    a.ctl = ctl;
-    a.cur = ctl + kCoCtlWords;
-    a.trav = ctl + kCoCtlWords + kcap;
-    a.pairs = r.pairs;
-    a.pseg = r.pcap / kCoSegs;
-    a.hmeta = (int64_t*)hmd;
-    a.lvl_end = (int64_t*)hmd + r.m_lev;
-    a.lvl_trace = a.lvl_end + (size_t)kcap * kCoMaxLevels;
-    a.blk_bytes = (int64_t*)hmd + r.m_blk;
-    // HGX_OPT_CO_TIMEOUT (per graph, read per launch): tests force the timeout path with a few ticks
-    a.timeout = g->co_timeout > 0 ? (u64)g->co_timeout : kCoTimeout;
-}
+    // A launch finished cleanly: block 0 left the level loop normally with both status words clear, and no
+    // block timed out on a barrier.
+    bool clean() const { return status() == 0 && !timed_out(); }
 
-// A launch finished cleanly: block 0 left the level loop normally with both status words clear, and no
-// block timed out on a barrier.
-bool co_clean(const CoRun& r) { return r.hm[0] == 0 && r.hm[3] == 0; }
-
-void co_launch(hgx_graph* g, CoRun& r) {
-    if (co_threads() == 512) hgx_bfs_coop<512><<<(unsigned)g->co_ok, 512, 0, g->stream>>>(r.a);
-    else hgx_bfs_coop<kCoThreads><<<(unsigned)g->co_ok, kCoThreads, 0, g->stream>>>(r.a);
-    HGX_CHECK_LAUNCH();
-}
-
-// A finished launch (status 0) over the seeds sidx (its seed j = batch index sidx[j]) -> out; the
-// result takes the pair list.
-void co_collect(hgx_graph* g, CoRun& r, const std::vector<int32_t>& sidx, BlockSet& out) {
-    const int32_t k = (int32_t)sidx.size();
-    const int64_t* hm = r.hm;
-    const int32_t nlev = (int32_t)hm[1];   // level counts per seed from the per-level atom counts
-    static const bool trace = trace_env("HGX_CO_TRACE");
-    if (trace) {   // per level: microseconds since the first level, work items
-        const int64_t* tr = hm + r.m_lev + (size_t)r.a.kcap * kCoMaxLevels;
-        std::fprintf(stderr, "[hgx coop] k=%d levels=%d:", k, nlev);
-        for (int32_t d = 0; d < nlev; ++d)
-            std::fprintf(stderr, " %.1f/%lld", (tr[2 * d] - tr[0]) / 100.0, (long long)tr[2 * d + 1]);
-        std::fprintf(stderr, "\n");
+    // Buffers and arguments of a launch over k seeds (k = -1: the workgroup stage's hand-over, up to kcap
+    // seeds); the control words are cleared on the stream.
+    void setup(int32_t k, int32_t kcap, int32_t max_depth, const hgx_algen_opts& o) {
+        hipStream_t st = g->stream;
+        const int mode = mode_of(o);
+        ensure_co_vis(g, std::max<int64_t>(kcap, 8));
+        if (g->co_pcap == 0) g->co_pcap = (int64_t)1 << 22;
+        if (g->co_fr == 0) g->co_fr = (int64_t)1 << 21;
+        const int64_t fr_seg = g->co_fr / kCoSegs;   // work items per segment and level
+        pcap = g->co_pcap;
+        int4* fr = (int4*)sc.take(sizeof(int4) * 3 * kCoSegs * (size_t)fr_seg);
+        pairs = (int2*)g->alloc(sizeof(int2) * (size_t)pcap);
+        const size_t ctl_words = kCoCtlWords + 2 * (size_t)kcap;
+        const size_t ctl_bytes = sizeof(u64) * ctl_words + 2 * sizeof(int32_t) * (size_t)kcap;
+        u64* ctl = (u64*)sc.take(ctl_bytes);
+        int32_t* sel_idx = (int32_t*)(ctl + ctl_words);
+        HGX_HIP(hipMemsetAsync(ctl, 0, ctl_bytes, st));
+        a.k = k;
+        a.kcap = kcap;
+        hb = take_host_buf(g, sizeof(int64_t) * (m_blk() + kCoMaxBlocks));
+        hm = (int64_t*)hb.p;
+        hm[0] = -1;
+        hm[1] = 0;
+        hm[2] = k;
+        hm[3] = 0;
+        int64_t* hmd = nullptr;
+        HGX_HIP(hipHostGetDevicePointer((void**)&hmd, hm, 0));
+        a.sel_idx = sel_idx;
+        a.seeds = sel_idx + kcap;
+        a.inc_off = g->inc_off;
+        a.inc_row = g->inc_row;
+        a.inc_type = g->inc_type;
+        a.yf = mode != kSym ? g->inc_yf : nullptr;
+        stage_items(g, mode, o, a);
+        a.tgt_off = g->tgt_off;
+        a.tgt_idx = g->tgt_idx;
+        a.want_type = o.link_type;
+        a.min_arity = o.return_source ? 1 : 2;
+        a.mode = mode;
+        a.maxd = max_depth < 0 ? INT32_MAX : max_depth;
+        static const int chunk_env = ab_int("HGX_CO_CHUNK", 0);
+        a.chunk = chunk_env > 0 ? std::min(chunk_env, 1 << 20) : kCoChunk;   // entries < 2^23 (co_item)
+        static const int bg_env = ab_int("HGX_CO_BARGROUPS", 0);   // A/B builds
+        a.bgroups = bg_env > 0 ? std::min(bg_env, kCoBarGroups) : 1;
+        static const bool lite_off = ab_int("HGX_CO_LITE", 1) == 0;   // A/B builds
+        a.lite = lite_off ? 0 : 1;
+        a.vwords = g->A / 64 + 1;
+        a.vis = g->co_vis;
+        a.fr = fr;
+        a.fr_seg = fr_seg;
+        a.ctl = ctl;
+        a.cur = ctl + kCoCtlWords;
+        a.trav = ctl + kCoCtlWords + kcap;
+        a.pairs = pairs;
+        a.pseg = pcap / kCoSegs;
+        a.hmeta = hmd;
+        a.lvl_end = hmd + m_lev();
+        a.lvl_trace = a.lvl_end + (size_t)kcap * kCoMaxLevels;
+        a.blk_bytes = hmd + m_blk();
+        // HGX_OPT_CO_TIMEOUT (per graph, read per launch): tests force the timeout path with a few ticks
+        a.timeout = g->co_timeout > 0 ? (u64)g->co_timeout : kCoTimeout;
     }
-    out.co_pairs = r.pairs;
-    out.co_bytes = sizeof(int2) * (size_t)r.pcap;
-    out.co_pseg = r.a.pseg;
-    r.pairs = nullptr;
-    out.co_segn.assign(hm + r.m_seg, hm + r.m_seg + kCoSegs);
-    out.co_n = 0;
-    for (int64_t c : out.co_segn) out.co_n += c;
-    out.co_idx = sidx;
-    out.co_lcnt.assign((size_t)k, {});
-    out.co_atoms.assign((size_t)k, {});
-    for (int32_t j = 0; j < k; ++j) {
-        const int64_t* le = hm + r.m_lev + (int64_t)j * kCoMaxLevels;
-        std::vector<int32_t>& lc = out.co_lcnt[j];
-        int64_t prev = 0;
-        for (int32_t d = 0; d < nlev; ++d) {
-            lc.push_back((int32_t)(le[d] - prev));
-            prev = le[d];
+
+    void launch() {
+        if (co_threads() == 512) hgx_bfs_coop<512><<<(unsigned)g->co_ok, 512, 0, g->stream>>>(a);
+        else hgx_bfs_coop<kCoThreads><<<(unsigned)g->co_ok, kCoThreads, 0, g->stream>>>(a);
+        HGX_CHECK_LAUNCH();
+    }
+
+    // A clean launch over the seeds sidx (its seed j = batch index sidx[j]) -> out; the result takes the pair list.
+    void collect(const std::vector<int32_t>& sidx, BlockSet& out) {
+        const int32_t k = (int32_t)sidx.size();
+        const int32_t nlev = n_levels();   // level counts per seed from the per-level atom counts
+        static const bool trace = trace_env("HGX_CO_TRACE");
+        if (trace) {   // per level: microseconds since the first level, work items
+            const int64_t* tr = level_trace();
+            std::fprintf(stderr, "[hgx coop] k=%d levels=%d:", k, nlev);
+            for (int32_t d = 0; d < nlev; ++d)
+                std::fprintf(stderr, " %.1f/%lld", (tr[2 * d] - tr[0]) / 100.0, (long long)tr[2 * d + 1]);
+            std::fprintf(stderr, "\n");
         }
-        while (!lc.empty() && lc.back() == 0) lc.pop_back();
-        const int32_t i = sidx[j];
-        out.pairs[i] = (int32_t)hm[4 + 2 * j];
-        out.levels[i] = (int32_t)lc.size();
-        out.lcnt[i] = lc.data();
-        out.atoms[i] = nullptr;   // block_materialize
-        out.traversed += (double)hm[5 + 2 * j];
+        out.co_pairs = pairs;
+        out.co_bytes = sizeof(int2) * (size_t)pcap;
+        out.co_pseg = a.pseg;
+        pairs = nullptr;
+        out.co_segn.assign(seg_pairs(), seg_pairs() + kCoSegs);
+        out.co_n = 0;
+        for (int64_t c : out.co_segn) out.co_n += c;
+        out.co_idx = sidx;
+        out.co_lcnt.assign((size_t)k, {});
+        out.co_atoms.assign((size_t)k, {});
+        for (int32_t j = 0; j < k; ++j) {
+            const int64_t* le = level_ends(j);
+            std::vector<int32_t>& lc = out.co_lcnt[j];
+            int64_t prev = 0;
+            for (int32_t d = 0; d < nlev; ++d) {
+                lc.push_back((int32_t)(le[d] - prev));
+                prev = le[d];
+            }
+            while (!lc.empty() && lc.back() == 0) lc.pop_back();
+            const int32_t i = sidx[j];
+            out.pairs[i] = (int32_t)pairs_of(j);
+            out.levels[i] = (int32_t)lc.size();
+            out.lcnt[i] = lc.data();
+            out.atoms[i] = nullptr;   // block_materialize
+            out.traversed += (double)traversed_of(j);
+        }
+        out.expanded = std::max(out.expanded, nlev);
+        out.co_bytes_alg = block_bytes() + 16.0 * (double)out.co_n;   // + the pairs and the bitmap words cleared
     }
-    out.expanded = std::max(out.expanded, nlev);
-    double bytes = 0;
-    for (int b = 0; b < g->co_ok; ++b) bytes += (double)hm[r.m_blk + b];
-    out.co_bytes_alg = bytes + 16.0 * (double)out.co_n;   // + the pairs and the bitmap words cleared
-}
 
-// A launch that did not finish: the bitmaps may hold bits of atoms no pair records, so they are
-// cleared whole; true when only capacities were short (the pair list grown to what was found, a
-// level's work items doubled: run again).  A segment's share of a level depends on which blocks find
-// its atoms, so a level near the capacity overflows one segment on some runs and not on others.
-bool co_failed(hgx_graph* g, CoRun& r, bool may_grow) {
-    const int64_t vwords = g->A / 64 + 1;
-    HGX_HIP(hipMemsetAsync(g->co_vis, 0, sizeof(u64) * (size_t)(g->co_vis_seeds * vwords), g->stream));
-    if (r.hm[3] != 0) ++g->co_timeouts;   // a barrier timed out: the rows engine takes the seeds
-    static const bool trace = trace_env("HGX_CO_TRACE");
-    if (trace)
-        std::fprintf(stderr, "[hgx coop] k=%d status=%lld timeout=%lld\n", r.a.k, (long long)r.hm[0], (long long)r.hm[3]);
-    const int64_t st = r.hm[0];
-    if (st <= 0 || (st & ~3ll) != 0 || r.hm[3] != 0 || !may_grow) return false;
-    if (st & 2) {
-        int64_t most = 0;
-        for (int q = 0; q < kCoSegs; ++q) most = std::max(most, r.hm[r.m_seg + q]);
-        g->co_pcap = std::max<int64_t>(2 * r.pcap, kCoSegs * (most + most / 4 + 64));
+    // A launch that did not finish (the bitmaps are cleared); true when only capacities were short (the pair
+    // list grown to what was found, a level's work items doubled: run again).  A segment's share of a level
+    // depends on which blocks find its atoms, so a level near the capacity overflows one segment on some runs
+    // and not on others.
+    bool failed(bool may_grow) {
+        clear_co_vis(g);
+        if (timed_out()) ++g->co_timeouts;   // a barrier timed out: the rows engine takes the seeds
+        static const bool trace = trace_env("HGX_CO_TRACE");
+        if (trace)
+            std::fprintf(stderr, "[hgx coop] k=%d status=%lld timeout=%lld\n", a.k, (long long)status(), (long long)hm[3]);
+        const int64_t st = status();
+        if (st <= 0 || (st & ~3ll) != 0 || timed_out() || !may_grow) return false;
+        if (st & 2) {
+            const int64_t most = std::max<int64_t>(0, *std::max_element(seg_pairs(), seg_pairs() + kCoSegs));
+            g->co_pcap = std::max<int64_t>(2 * pcap, kCoSegs * (most + most / 4 + 64));
+        }
+        if (st & 1) {
+            constexpr int64_t kFrMost = (int64_t)1 << 24;   // 768 MiB of work items over the three slots
+            if (g->co_fr >= kFrMost) return false;
+            g->co_fr = std::min(2 * g->co_fr, kFrMost);
+        }
+        return true;
     }
-    if (st & 1) {
-        constexpr int64_t kFrMost = (int64_t)1 << 24;   // 768 MiB of work items over the three slots
-        if (g->co_fr >= kFrMost) return false;
-        g->co_fr = std::min(2 * g->co_fr, kFrMost);
-    }
-    return true;
-}
-
-float ev_ms(hgx_graph* g, hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    HGX_HIP(hipEventElapsedTime(&ms, a, b));
-    return ms;
-}
+};
 
 // The multi-workgroup stage over the seeds sidx (indices into seeds); true when they finished there
 // (false: a capacity or the grid did not fit, and the rows engine takes them).
@@ -5211,30 +5373,22 @@ bool bfs_coop(hgx_graph* g, const int32_t* seeds, const std::vector<int32_t>& si
     if (k == 0 || k > kMaxCoSeeds || !co_fits(g)) return false;
     for (int attempt = 0; attempt < 3; ++attempt) {
         CoRun r(g);
-        co_setup(g, r, k, k, max_depth, o);
+        r.setup(k, k, max_depth, o);
         int32_t* hs = (int32_t*)g->pinned_buf(sizeof(int32_t) * (size_t)k);
         for (int32_t j = 0; j < k; ++j) hs[j] = seeds[sidx[j]];
         HGX_HIP(hipMemcpyAsync(const_cast<int32_t*>(r.a.seeds), hs, sizeof(int32_t) * (size_t)k,
                                hipMemcpyHostToDevice, st));
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        if (g->timing) {
-            ev[0] = ev_take(g);
-            ev[1] = ev_take(g);
-            HGX_HIP(hipEventRecord(ev[0], st));
-        }
-        co_launch(g, r);
-        if (ev[1]) HGX_HIP(hipEventRecord(ev[1], st));
+        EvTimer t(g);
+        t.start();
+        r.launch();
+        t.stop();
         spin_sync(st);
-        if (ev[1]) {
-            out.co_ms += ev_ms(g, ev[0], ev[1]);
-            ev_give(g, ev[0]);
-            ev_give(g, ev[1]);
-        }
-        if (co_clean(r)) {
-            co_collect(g, r, sidx, out);
+        out.co_ms += t.ms();
+        if (r.clean()) {
+            r.collect(sidx, out);
             return true;
         }
-        if (!co_failed(g, r, attempt < 2)) return false;
+        if (!r.failed(attempt < 2)) return false;
     }
     return false;
 }
@@ -5251,15 +5405,10 @@ void sc_tab_reset(hgx_graph* g) {
     HGX_HIP(hipMemsetAsync((char*)g->sc_tab + hb, 0, kScTabBytes - hb, g->stream));
 }
 
-int sc_fits(hgx_graph* g) {   // its grid (0: does not fit); the same residency rule as co_fits
+int sc_fits(hgx_graph* g) {   // its grid (0: does not fit)
     if (g->sc_ok < 0) {
-        int per_cu = 0, cus = 0;
-        HGX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hgx_seq_coop<256>, 256, 0));
-        HGX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->device));
-        const int64_t blocks = (int64_t)std::min(per_cu - 1, 2) * cus;
         static const int cap_env = ab_int("HGX_SC_BLOCKS", 0);   // A/B builds
-        const int64_t cap = cap_env >= kCoMinBlocks ? std::min(cap_env, kCoMaxBlocks) : kCoBlocks;
-        g->sc_ok = blocks >= kCoMinBlocks ? (int32_t)std::min<int64_t>(blocks, cap) : 0;
+        g->sc_ok = resident_grid(g, hgx_seq_coop<256>, 256, cap_env);
     }
     return g->sc_ok;
 }
@@ -5282,30 +5431,33 @@ struct ScRun {
     int32_t* hl = nullptr;
     int32_t* ha = nullptr;
     int64_t* hc = nullptr;
-    int64_t* hm = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    EvTimer timer;
     int2* chain_buf = nullptr;      // (chained) the workgroup engine's list and its length
     uint32_t* chain_cnt = nullptr;
-    explicit ScRun(hgx_graph* gg) : g(gg), w{gg, {}} {}
+    explicit ScRun(hgx_graph* gg) : g(gg), w{gg, {}}, timer(gg) {}
     ~ScRun() {
-        if (ev[0]) ev_give(g, ev[0]);
-        if (ev[1]) ev_give(g, ev[1]);
         std::lock_guard<std::mutex> lk(g->seq_mu);
         if (hb.p) g->seq_hbufs.push_back(hb);
         if (pb.p && !keep_pb) g->seq_hbufs.push_back(pb);
     }
+    // The mapped readout (ScArgs::hmeta): [0] status (-1 until the kernel's end), [1] levels, [2] pairs, [3] set
+    // by a block that timed out on a grid barrier, [5] seeds (chained: how many the kernel took) | bytes [nblk] |
+    // traversed [nblk] | the chained seeds' indices [kMaxCoSeeds] | trace [3][kCoMaxLevels] (HGX_CO_TRACE)
+    int64_t* hm = nullptr;
+    int64_t status() const { return hm[0]; }
+    int32_t n_levels() const { return (int32_t)hm[1]; }
+    int64_t n_pairs() const { return hm[2]; }
+    bool timed_out() const { return hm[3] != 0; }
+    int64_t seeds_taken() const { return hm[5]; }
+    bool clean() const { return status() == 0 && !timed_out(); }
+    double block_bytes(int b) const { return (double)hm[8 + b]; }
+    double block_traversed(int b) const { return (double)hm[8 + nblk + b]; }
+    int32_t chained_index(int64_t j) const { return (int32_t)hm[8 + 2 * (size_t)nblk + j]; }   // entry j's batch index
+    const int64_t* level_trace() const { return hm + 8 + 2 * (size_t)nblk + kMaxCoSeeds; }
     // chain: the seeds come from the workgroup engine's list (a.chain / a.chain_n, zeroed here)
     void prepare(const YieldAdj* ya, int32_t maxd, bool chain) {
         hipStream_t st = g->stream;
-        const int64_t vwords = g->A / 64 + 1;
-        if (g->co_vis_seeds < kMaxCoSeeds) {   // the grid stages' zero-invariant bitmaps (shared with hgx_bfs_coop)
-            if (g->co_vis) HGX_HIP(hipFree(g->co_vis));
-            g->co_vis = nullptr;
-            g->co_vis_seeds = 0;
-            HGX_HIP(hipMalloc(&g->co_vis, sizeof(u64) * (size_t)(kMaxCoSeeds * vwords)));
-            HGX_HIP(hipMemsetAsync(g->co_vis, 0, sizeof(u64) * (size_t)(kMaxCoSeeds * vwords), st));
-            g->co_vis_seeds = kMaxCoSeeds;
-        }
+        ensure_co_vis(g, kMaxCoSeeds);
         if (!g->sc_tab) {   // the stage's tables, empty between calls (a clean launch leaves them so)
             HGX_HIP(hipMalloc(&g->sc_tab, kScTabBytes));
             sc_tab_reset(g);
@@ -5317,7 +5469,7 @@ struct ScRun {
         a.a_tgt = ya->tgt;
         a.a_lnk = ya->lnk;
         a.maxd = maxd;
-        a.vwords = vwords;
+        a.vwords = g->A / 64 + 1;
         a.vis = g->co_vis;
         a.hbits = kScHashBits;                      // 512K slots: a level holds <= kScKeyCap discoveries
         a.hmask = ((int64_t)1 << a.hbits) - 1;
@@ -5346,8 +5498,6 @@ struct ScRun {
         }
         nblk = g->sc_ok;
         trace = trace_env("HGX_CO_TRACE");
-        // mapped: [0, 8) status, levels, pairs, timed out, -, seeds | bytes [nblk] | traversed [nblk] | the chained
-        // seeds' indices [kMaxCoSeeds] | trace
         hb = take_host_buf(g, sizeof(int64_t) * (8 + 2 * (size_t)nblk + kMaxCoSeeds + (trace ? 3 * (size_t)kCoMaxLevels : 0)));
         hm = (int64_t*)hb.p;
         hm[0] = -1;
@@ -5373,48 +5523,37 @@ struct ScRun {
     }
     void launch() {
         hipStream_t st = g->stream;
-        if (g->timing) {
-            ev[0] = ev_take(g);
-            ev[1] = ev_take(g);
-            HGX_HIP(hipEventRecord(ev[0], st));
-        }
+        timer.start();
         hgx_seq_coop<256><<<(unsigned)nblk, 256, 0, st>>>(a);
         HGX_CHECK_LAUNCH();
-        if (ev[1]) HGX_HIP(hipEventRecord(ev[1], st));
+        timer.stop();
         seq_mark("grid stage enqueued");
     }
     // After the launch finished: the k seeds' results (seed j of the launch -> out.segs[sidx[j]]).  1: done;
     // 0: not clean (the bitmaps and tables reset; the caller runs the seeds elsewhere); 2: only the pairs
     // outgrew their buffer (the capacity grown on the graph: run once more)
     int collect(int32_t k, const std::vector<int32_t>& sidx, SeqOut& out, double* ms) {
-        hipStream_t st = g->stream;
-        if (ev[1]) {
-            *ms += ev_ms(g, ev[0], ev[1]);
-            ev_give(g, ev[0]);
-            ev_give(g, ev[1]);
-            ev[0] = ev[1] = nullptr;
-        }
-        const bool clean = hm[0] == 0 && hm[3] == 0;
+        *ms += timer.ms();
         if (trace) {   // per level: P1 (expand + barrier) and P2 (emit) in microseconds of block 0's clock (100 MHz)
             std::fprintf(stderr, "[hgx seq coop] k=%d status=%lld timeout=%lld levels=%lld pairs=%lld; us P1/P2:", k,
                          (long long)hm[0], (long long)hm[3], (long long)hm[1], (long long)hm[2]);
-            const int64_t* tr = hm + 8 + 2 * (size_t)nblk + kMaxCoSeeds;
+            const int64_t* tr = level_trace();
             for (int64_t d = 0; d < hm[1] && d < kCoMaxLevels; ++d)
                 std::fprintf(stderr, " %.1f/%.1f", (tr[3 * d + 1] - tr[3 * d]) * 0.01, (tr[3 * d + 2] - tr[3 * d + 1]) * 0.01);
             std::fprintf(stderr, "\n");
         }
-        if (!clean) {   // the bitmaps may hold bits no pair records, the tables entries: cleared whole
-            if (hm[3] != 0) ++g->co_timeouts;
-            HGX_HIP(hipMemsetAsync(g->co_vis, 0, sizeof(u64) * (size_t)(g->co_vis_seeds * (g->A / 64 + 1)), st));
+        if (!clean()) {   // the bitmaps may hold bits no pair records, the tables entries: cleared whole
+            if (timed_out()) ++g->co_timeouts;
+            clear_co_vis(g);
             sc_tab_reset(g);
-            if (hm[0] == 2 && hm[3] == 0) {   // only the pairs outgrew their buffer
+            if (status() == 2 && !timed_out()) {   // only the pairs outgrew their buffer
                 g->sc_pcap = a.pcap * 4;
                 return 2;
             }
             return 0;
         }
-        const int32_t nlev = (int32_t)hm[1];
-        const int64_t total = hm[2];
+        const int32_t nlev = n_levels();
+        const int64_t total = n_pairs();
         if (total > a.pcap || nlev > kCoMaxLevels) fail(HGX_E_DEVICE, "hgx_bfs_sequence: grid stage sizes inconsistent");
         keep_pb = true;
         out.bufs.push_back(pb);
@@ -5424,7 +5563,7 @@ struct ScRun {
             int64_t o = o0;
             for (int32_t j = 0; j < k; ++j) {
                 const int64_t c = hc[64 * (size_t)d + j];
-                if (c > 0) out.segs[(size_t)sidx[j]].push_back({hl + o, ha + o, nullptr, c, d + 1});
+                if (c > 0) out.segs[(size_t)sidx[j]].push_back(Seg::plain(hl + o, ha + o, nullptr, c, d + 1));
                 if (c > 0) out.deepest = std::max(out.deepest, d + 1);
                 o += c;
             }
@@ -5432,8 +5571,8 @@ struct ScRun {
         }
         if (o0 != total) fail(HGX_E_DEVICE, "hgx_bfs_sequence: grid stage pair counts inconsistent");
         for (int b = 0; b < nblk; ++b) {
-            out.bytes += (double)hm[8 + b];
-            out.traversed += (double)hm[8 + nblk + b];
+            out.bytes += block_bytes(b);
+            out.traversed += block_traversed(b);
         }
         return 1;
     }
@@ -5465,106 +5604,61 @@ bool seq_coop(hgx_graph* g, const int32_t* seeds, const std::vector<int32_t>& si
     return false;
 }
 
-}  // namespace
+// ---- the two workgroup stages (hgx_seq_block, hgx_bfs_block), host side ----
 
-void bfs_block(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth, const hgx_algen_opts& o,
-               BlockSet& out) {
-    hipStream_t st = g->stream;
-    const int64_t timeouts0 = g->co_timeouts;
-    struct Fallbacks {   // the call's grid launches that fell back (counted by co_failed)
-        hgx_graph* g;
-        int64_t t0;
-        BlockSet& out;
-        ~Fallbacks() { out.co_fallbacks = (int32_t)(g->co_timeouts - t0); }
-    } fb{g, timeouts0, out};
-    const int mode = mode_of(o);
-    if (mode != kSym) ensure_inc_yield(g);
-    out.seeds.assign(seeds, seeds + n_seeds);
-    out.atoms.assign((size_t)n_seeds, nullptr);
-    out.lcnt.assign((size_t)n_seeds, nullptr);
-    out.pairs.assign((size_t)n_seeds, -1);
-    out.levels.assign((size_t)n_seeds, 0);
-    BbArgs a{};
-    a.inc_off = g->inc_off;
-    a.inc_row = g->inc_row;
-    a.inc_type = g->inc_type;
-    a.yf = mode != kSym ? g->inc_yf : nullptr;
-    a.tgt_off = g->tgt_off;
-    a.tgt_idx = g->tgt_idx;
-    a.want_type = o.link_type;
-    a.min_arity = o.return_source ? 1 : 2;
-    a.mode = mode;
-    a.maxd = max_depth < 0 ? INT32_MAX : max_depth;
-    stage_items(g, mode, o, a);
-    const size_t per_seed = (size_t)kBbPairs * 8 + 32;
-    // The grid stage goes on the stream right behind the workgroup launches and reads their overflow
-    // list itself: one wait for both (HGX_CO_CHAIN=0, for A/B: a host round trip in between).
-    static const bool chain_env = ab_int("HGX_CO_CHAIN", 1) != 0;
-    std::unique_ptr<CoRun> cr;
-    if (g->bfs_block == 1 && chain_env && n_seeds > 0 && co_fits(g)) {
-        cr.reset(new CoRun(g));
-        co_setup(g, *cr, -1, kMaxCoSeeds, max_depth, o);
-        a.sel_n = cr->a.ctl + kCoSel;
-        a.sel_idx = const_cast<int32_t*>(cr->a.sel_idx);
-        a.sel_seed = const_cast<int32_t*>(cr->a.seeds);
-        a.sel_cap = kMaxCoSeeds;
+// The seeds of a workgroup-stage call on the device: launches of more than kSbInline seeds read them there
+// (smaller ones take theirs in the kernel arguments).  Back to the pool with the object, or at reset().
+struct SeedUpload {
+    PoolScratch w;
+    int32_t* d = nullptr;
+    SeedUpload(hgx_graph* g, const int32_t* seeds, int32_t n_seeds) : w{g, {}} {
+        if (n_seeds <= kSbInline) return;
+        const size_t bytes = sizeof(int32_t) * (size_t)n_seeds;
+        d = (int32_t*)w.take(bytes);
+        int32_t* hs = (int32_t*)g->pinned_buf(bytes);
+        std::memcpy(hs, seeds, bytes);
+        HGX_HIP(hipMemcpyAsync(d, hs, bytes, hipMemcpyHostToDevice, g->stream));
     }
-    int32_t* dseeds = nullptr;
-    size_t dseeds_n = 0;
-    if (n_seeds > kSbInline) {
-        dseeds_n = sizeof(int32_t) * (size_t)n_seeds;
-        dseeds = (int32_t*)g->alloc(dseeds_n);
-        int32_t* hs = (int32_t*)g->pinned_buf(dseeds_n);
-        std::memcpy(hs, seeds, dseeds_n);
-        HGX_HIP(hipMemcpyAsync(dseeds, hs, dseeds_n, hipMemcpyHostToDevice, st));
+    void reset() {
+        w.give_back();
+        d = nullptr;
     }
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    if (g->timing) {
-        for (auto& e : ev) e = ev_take(g);
-        HGX_HIP(hipEventRecord(ev[0], st));
-    }
-    struct Chunk {
-        int64_t c0, nb;
-        char* h;
-    };
-    std::vector<Chunk> chunks;
-    // HGX_OPT_BFS_BLOCK 2 (tests): every seed straight to the multi-workgroup stage
-    for (int64_t c0 = 0; c0 < (g->bfs_block == 2 ? 0 : n_seeds); c0 += kBbChunk) {
-        const int64_t nb = std::min<int64_t>(kBbChunk, n_seeds - c0);
+};
+
+struct StageChunk {   // one launch: the seeds [c0, c0 + nb) and its mapped output
+    int64_t c0, nb;
+    char* h;
+};
+
+// The launches of a workgroup stage over the first n seeds, `chunk` seeds each.  Per launch: a mapped buffer of
+// per_seed bytes a seed (bufs owns it), the seeds in the arguments or from `up`, then launch(c0, nb, d), which
+// lays the buffer (device address d) out in a and launches the kernel.
+template <class Args, class Launch>
+std::vector<StageChunk> launch_stage_chunks(hgx_graph* g, const int32_t* seeds, int64_t n, int64_t chunk, size_t per_seed,
+                                            const SeedUpload& up, std::vector<PoolBuf>& bufs, Args& a, Launch&& launch) {
+    std::vector<StageChunk> chunks;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int64_t nb = std::min<int64_t>(chunk, n - c0);
         PoolBuf hb = take_host_buf(g, per_seed * (size_t)nb);
-        out.bufs.push_back(hb);
+        bufs.push_back(hb);
         void* dv = nullptr;
         HGX_HIP(hipHostGetDevicePointer(&dv, hb.p, 0));
-        char* d = (char*)dv;
-        // layout: meta [4 nb] int64 | atoms [nb * kBbPairs] | level counts [nb * kBbPairs]
         a.n = (int32_t)nb;
-        a.base = (int32_t)c0;
-        a.meta = (int64_t*)d;
-        a.out_atom = (int32_t*)(d + 32 * nb);
-        a.out_cnt = a.out_atom + nb * kBbPairs;
         if (nb <= kSbInline) {   // the kernel reads the inline seeds whenever n <= kSbInline
             for (int64_t i = 0; i < nb; ++i) a.seed_inline[i] = seeds[c0 + i];
             a.seeds = nullptr;
         } else {
-            a.seeds = dseeds + c0;
+            a.seeds = up.d + c0;
         }
-        hgx_bfs_block<<<(unsigned)nb, kBbThreads, 0, st>>>(a);
+        launch(c0, nb, (char*)dv);
         HGX_CHECK_LAUNCH();
         chunks.push_back({c0, nb, (char*)hb.p});
     }
-    if (ev[1]) HGX_HIP(hipEventRecord(ev[1], st));
-    if (cr) {
-        co_launch(g, *cr);
-        if (ev[2]) HGX_HIP(hipEventRecord(ev[2], st));
-    }
-    spin_sync(st);
-    int64_t nsel = cr ? cr->hm[2] : 0;   // seeds the chained grid stage took (> kMaxCoSeeds: none run)
-    if (ev[1]) {
-        out.ms = ev_ms(g, ev[0], ev[1]);
-        if (cr && nsel > 0 && nsel <= kMaxCoSeeds) out.co_ms += ev_ms(g, ev[1], ev[2]);
-        for (auto& e : ev) ev_give(g, e);
-    }
-    if (dseeds) g->release(dseeds, dseeds_n);
+    return chunks;
+}
+
+// The set-mode launches' mapped output -> out: per seed its atoms and level counts, or its place in out.rerun.
+void block_read_meta(const std::vector<StageChunk>& chunks, BlockSet& out) {
     for (auto& c : chunks) {
         const int64_t* meta = (const int64_t*)c.h;
         const int32_t* at = (const int32_t*)(c.h + 32 * c.nb);
@@ -5584,6 +5678,75 @@ void bfs_block(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_
             out.lcnt[si] = lc + i * kBbPairs;
         }
     }
+}
+
+}  // namespace
+
+void bfs_block(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth, const hgx_algen_opts& o,
+               BlockSet& out) {
+    hipStream_t st = g->stream;
+    struct Fallbacks {   // the call's grid launches that fell back (counted by CoRun::failed)
+        hgx_graph* g;
+        int64_t t0;
+        BlockSet& out;
+        ~Fallbacks() { out.co_fallbacks = (int32_t)(g->co_timeouts - t0); }
+    } fb{g, g->co_timeouts, out};
+    const int mode = mode_of(o);
+    if (mode != kSym) ensure_inc_yield(g);
+    out.seeds.assign(seeds, seeds + n_seeds);
+    out.atoms.assign((size_t)n_seeds, nullptr);
+    out.lcnt.assign((size_t)n_seeds, nullptr);
+    out.pairs.assign((size_t)n_seeds, -1);
+    out.levels.assign((size_t)n_seeds, 0);
+    BbArgs a{};
+    a.inc_off = g->inc_off;
+    a.inc_row = g->inc_row;
+    a.inc_type = g->inc_type;
+    a.yf = mode != kSym ? g->inc_yf : nullptr;
+    a.tgt_off = g->tgt_off;
+    a.tgt_idx = g->tgt_idx;
+    a.want_type = o.link_type;
+    a.min_arity = o.return_source ? 1 : 2;
+    a.mode = mode;
+    a.maxd = max_depth < 0 ? INT32_MAX : max_depth;
+    stage_items(g, mode, o, a);
+    // The grid stage goes on the stream right behind the workgroup launches and reads their overflow
+    // list itself: one wait for both (HGX_CO_CHAIN=0, for A/B: a host round trip in between).
+    static const bool chain_env = ab_int("HGX_CO_CHAIN", 1) != 0;
+    std::unique_ptr<CoRun> cr;
+    if (g->bfs_block == 1 && chain_env && n_seeds > 0 && co_fits(g)) {
+        cr.reset(new CoRun(g));
+        cr->setup(-1, kMaxCoSeeds, max_depth, o);
+        a.sel_n = cr->a.ctl + kCoSel;
+        a.sel_idx = const_cast<int32_t*>(cr->a.sel_idx);
+        a.sel_seed = const_cast<int32_t*>(cr->a.seeds);
+        a.sel_cap = kMaxCoSeeds;
+    }
+    SeedUpload up(g, seeds, n_seeds);
+    EvTimer t(g);   // start .. mark: the workgroup launches; mark .. stop: the chained grid stage
+    t.start();
+    // HGX_OPT_BFS_BLOCK 2 (tests): every seed straight to the multi-workgroup stage
+    const auto chunks = launch_stage_chunks(
+        g, seeds, g->bfs_block == 2 ? 0 : n_seeds, kBbChunk, (size_t)kBbPairs * 8 + 32, up, out.bufs, a,
+        [&](int64_t c0, int64_t nb, char* d) {
+            // layout: meta [4 nb] int64 | atoms [nb * kBbPairs] | level counts [nb * kBbPairs]
+            a.base = (int32_t)c0;
+            a.meta = (int64_t*)d;
+            a.out_atom = (int32_t*)(d + 32 * nb);
+            a.out_cnt = a.out_atom + nb * kBbPairs;
+            hgx_bfs_block<<<(unsigned)nb, kBbThreads, 0, st>>>(a);
+        });
+    t.mark();
+    if (cr) {
+        cr->launch();
+        t.stop();
+    }
+    spin_sync(st);
+    const int64_t nsel = cr ? cr->seeds_taken() : 0;   // seeds the chained grid stage took (> kMaxCoSeeds: none run)
+    if (t.on()) out.ms = t.ms_to_mark();
+    if (cr && nsel > 0 && nsel <= kMaxCoSeeds) out.co_ms += t.ms_from_mark();
+    up.reset();
+    block_read_meta(chunks, out);
     if (g->bfs_block == 2)
         for (int32_t i = 0; i < n_seeds; ++i) out.rerun.push_back(i);
     if (cr) {
@@ -5591,14 +5754,14 @@ void bfs_block(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_
             throw std::runtime_error("hgx_bfs_batch: the grid stage took " + std::to_string(nsel) + " of " +
                                      std::to_string(out.rerun.size()) + " handed-over seeds");
         if (nsel == 0 || nsel > kMaxCoSeeds) return;   // none, or more than fit: the rows engine
-        std::vector<int32_t> sidx(cr->hm + cr->m_sel, cr->hm + cr->m_sel + nsel);   // the slots' order
-        if (co_clean(*cr)) {
-            co_collect(g, *cr, sidx, out);
+        const std::vector<int32_t> sidx(cr->batch_indices(), cr->batch_indices() + nsel);
+        if (cr->clean()) {
+            cr->collect(sidx, out);
             out.n_coop = (int32_t)nsel;
             out.rerun.clear();
             return;
         }
-        const bool again = co_failed(g, *cr, true);
+        const bool again = cr->failed(true);
         cr.reset();
         if (!again) return;
     }
@@ -5639,6 +5802,23 @@ void free_yield_lists(hgx_graph* g) {
     g->yadjs.clear();
 }
 
+namespace {
+// The first half of a per-atom list's build: count(cnt) launches the kernel that counts each atom's entries
+// into cnt [A + 1] (pool memory, cnt[A] = 0), off [A + 1] becomes their exclusive prefix sum; the total.
+template <class Count>
+int64_t yield_offsets(hgx_graph* g, int64_t* off, Count&& count) {
+    PoolScratch w{g, {}};
+    int64_t* cnt = (int64_t*)w.take(sizeof(int64_t) * (size_t)(g->A + 1));
+    count(cnt);
+    HGX_CHECK_LAUNCH();
+    exclusive_scan_i64(g, cnt, off, (size_t)g->A + 1);
+    int64_t n = 0;
+    HGX_HIP(hipMemcpyAsync(&n, off + g->A, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    HGX_HIP(hipStreamSynchronize(g->stream));
+    return n;
+}
+}  // namespace
+
 const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arity, bool rev) {
     if (mode == kSym && type < 0) return nullptr;   // every co-target of every entry: too large to keep
     hgx_graph* root = g->base ? g->base : g;         // built once on the snapshot, read by its contexts
@@ -5667,17 +5847,10 @@ const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arit
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((A + 3) / 4, 16384));
     int64_t* off = nullptr;
     HGX_HIP(hipMalloc(&off, sizeof(int64_t) * (size_t)(A + 1)));
-    a.cnt = (int64_t*)g->alloc(sizeof(int64_t) * (size_t)(A + 1));
-    hgx_ya_count<<<grid, 256, 0, st>>>(a);
-    HGX_CHECK_LAUNCH();
-    size_t tb = 0;
-    HGX_HIP(rocprim::exclusive_scan(nullptr, tb, a.cnt, off, (int64_t)0, (size_t)A + 1, rocprim::plus<int64_t>(), st));
-    void* tmp = g->alloc(tb);
-    HGX_HIP(rocprim::exclusive_scan(tmp, tb, a.cnt, off, (int64_t)0, (size_t)A + 1, rocprim::plus<int64_t>(), st));
-    HGX_HIP(hipMemcpyAsync(&y.n, off + A, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HGX_HIP(hipStreamSynchronize(st));
-    g->release(tmp, tb);
-    g->release(a.cnt, sizeof(int64_t) * (size_t)(A + 1));
+    y.n = yield_offsets(g, off, [&](int64_t* cnt) {
+        a.cnt = cnt;
+        hgx_ya_count<<<grid, 256, 0, st>>>(a);
+    });
     if (y.n * 8 > kYieldAdjBudget) {   // remembered as refused: the yield list serves instead
         HGX_HIP(hipFree(off));
         root->yadjs.push_back(y);
@@ -5710,17 +5883,9 @@ const YieldList* yield_list(hgx_graph* g, int mode, int32_t type) {
     HGX_HIP(hipMalloc(&y.off, sizeof(int64_t) * (size_t)(A + 1)));
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((A + 3) / 4, 16384));
     const uint8_t* yf = mode != kSym ? g->inc_yf : nullptr;
-    int64_t* cnt = (int64_t*)g->alloc(sizeof(int64_t) * (size_t)(A + 1));
-    hgx_yl_count<<<grid, 256, 0, st>>>(A, g->inc_off, g->inc_type, yf, mode, type, cnt);
-    HGX_CHECK_LAUNCH();
-    size_t tb = 0;
-    HGX_HIP(rocprim::exclusive_scan(nullptr, tb, cnt, y.off, (int64_t)0, (size_t)A + 1, rocprim::plus<int64_t>(), st));
-    void* tmp = g->alloc(tb);
-    HGX_HIP(rocprim::exclusive_scan(tmp, tb, cnt, y.off, (int64_t)0, (size_t)A + 1, rocprim::plus<int64_t>(), st));
-    HGX_HIP(hipMemcpyAsync(&y.n, y.off + A, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HGX_HIP(hipStreamSynchronize(st));
-    g->release(tmp, tb);
-    g->release(cnt, sizeof(int64_t) * (size_t)(A + 1));
+    y.n = yield_offsets(g, y.off, [&](int64_t* cnt) {
+        hgx_yl_count<<<grid, 256, 0, st>>>(A, g->inc_off, g->inc_type, yf, mode, type, cnt);
+    });
     HGX_HIP(hipMalloc(&y.row, sizeof(int32_t) * (size_t)std::max<int64_t>(y.n, 1)));
     hgx_yl_fill<<<grid, 256, 0, st>>>(A, g->inc_off, g->inc_row, g->inc_type, yf, mode, type, y.off, y.row);
     HGX_CHECK_LAUNCH();
@@ -5808,6 +5973,15 @@ struct hgx_seq_result {
     double ms_coop = 0, bytes_coop = 0;     // the order-exact grid stage (hgx_seq_coop): device ms, algorithmic bytes
     int32_t n_coop = 0;                     //   and the seeds it finished
     int32_t n_block = 0, n_level = 0;       // seeds finished by each engine
+    // The grid stage finished all n seeds handed to the later engines: its output is theirs.
+    void adopt(SeqOut&& co, int32_t n) {
+        lev.segs = std::move(co.segs);
+        lev.bufs = std::move(co.bufs);
+        lev.traversed = co.traversed;
+        lev.deepest = co.deepest;
+        bytes_coop = co.bytes;
+        n_coop = n;
+    }
     ~hgx_seq_result() {
         if (!g) return;
         settle();
@@ -5827,62 +6001,60 @@ struct hgx_seq_result {
     }
 };
 
-extern "C" {
+namespace {
 
-int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
-                     const hgx_algen_opts* opts, hgx_seq_result** out) {
-    HGX_API_BEGIN
-    if (!g || !out || n_seeds < 0 || (n_seeds > 0 && !seeds)) fail(HGX_E_INVALID, "hgx_bfs_sequence: bad argument");
-    *out = nullptr;
-    if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_bfs_sequence: not available on a partition shard");
-    // FIFO order and the discovering link follow the incidence order, i.e. rank order; after an
-    // update appended ranks whose handles may sort before existing ones that is not handle order
-    // (ADVICE r01), and no re-sort of the output can repair it.
-    if (!g->ranks_ordered)
-        fail(HGX_E_UNSUPPORTED, "hgx_bfs_sequence: ranks were appended by hgx_graph_update and may not follow "
-                                "handle order (re-assert with HGX_OPT_RANKS_ORDERED or rebuild the snapshot)");
-    hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
-    for (int32_t i = 0; i < n_seeds; ++i)
-        if (seeds[i] < 0 || seeds[i] >= g->A) fail(HGX_E_INVALID, "hgx_bfs_sequence: seed out of range");
-    if (max_depth < -1) fail(HGX_E_INVALID, "hgx_bfs_sequence: bad max_depth");
-    std::lock_guard<std::mutex> lk(g->mu);
-    SeqTrace trace;
-    g_seq_trace = trace.on ? &trace : nullptr;
-    struct TraceOff {
-        ~TraceOff() { g_seq_trace = nullptr; }
-    } trace_off;
-    HGX_HIP(hipSetDevice(g->device));
-    hipStream_t st = g->stream;
-    const int32_t maxd = max_depth < 0 ? INT32_MAX : max_depth;
-    const int mode = mode_of(o);
-
-    hgx_seq_result* r = new hgx_seq_result();
-    struct Guard {
-        hgx_seq_result* r;
-        ~Guard() { delete r; }
-    } guard{r};
-    r->g = g;
-    g->refs.fetch_add(1);
-    r->n_seeds = n_seeds;
-    r->blk.assign((size_t)n_seeds, Seg{nullptr, nullptr, nullptr, -1, 0});
-    r->lev_of.assign((size_t)n_seeds, -1);
-    std::vector<int64_t> cnt((size_t)n_seeds, 0);
-    seq_maxes(g);
-    if (mode != kSym) ensure_inc_yield(g);
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (g->timing) {
-        ev0 = ev_take(g);
-        ev1 = ev_take(g);
-        HGX_HIP(hipEventRecord(ev0, st));
+struct MappedClock {   // the HGX_SB_CLOCK trace's mapped buffer: per seed its start / end ticks
+    int64_t* p = nullptr;
+    ~MappedClock() {
+        if (p) (void)hipHostFree(p);
     }
-    seq_mark("call set up");
-    std::vector<int32_t> rerun;   // seed indices for the level-synchronous engine
+};
+
+// One hgx_bfs_sequence call (g->mu held, g's device current): the stages in order, each leaving the seeds it did
+// not finish to the next one.
+struct SeqCall {
+    hgx_graph* const g;
+    const int32_t* const seeds;
+    const int32_t n_seeds, maxd;
+    const hgx_algen_opts o;
+    const int mode;
+    const hipStream_t st;
+    hgx_seq_result* const r;
+    std::vector<int64_t> cnt;         // [n_seeds] pairs of each seed
+    std::vector<int32_t> rerun;       // indices of the seeds the workgroup stage did not finish, ascending
+    std::vector<int32_t> rs;          //   and their atoms
     int32_t deepest = 0;
     std::unique_ptr<ScRun> chained;   // the grid stage chained behind the workgroup launches
-    if (g->seq_engine == 0 && n_seeds > 0) {
-        const int kbits = bitlen(g->max_arity > 1 ? (u64)(g->max_arity - 1) : 0);
-        SbArgs a{};
+    EvTimer total;                    // the call; its mark: the end of the workgroup launches
+
+    SeqCall(hgx_graph* gg, const int32_t* sd, int32_t n, int32_t md, const hgx_algen_opts& oo, hgx_seq_result* rr)
+        : g(gg), seeds(sd), n_seeds(n), maxd(md), o(oo), mode(mode_of(oo)), st(gg->stream), r(rr), cnt((size_t)n, 0),
+          total(gg) {
+        r->n_seeds = n_seeds;
+        r->blk.assign((size_t)n_seeds, Seg::none());
+        r->lev_of.assign((size_t)n_seeds, -1);
+    }
+
+    void run() {
+        seq_maxes(g);
+        if (mode != kSym) ensure_inc_yield(g);
+        total.start();
+        seq_mark("call set up");
+        if (g->seq_engine == 0 && n_seeds > 0) {
+            workgroup_stage();
+        } else {
+            for (int32_t i = 0; i < n_seeds; ++i) rerun.push_back(i);
+        }
+        r->n_level = (int32_t)rerun.size();
+        r->n_block = n_seeds - r->n_level;
+        if (!rerun.empty()) later_stages();
+        finish();
+    }
+
+    // The workgroup stage's arguments but the launches' own; batches chain the grid stage behind the workgroup
+    // launches (no host round trip between the stages); a single traversal (the drop-in's next() shape) keeps its
+    // latency without the extra launch.
+    void bind_block(SbArgs& a) {
         a.inc_off = g->inc_off;
         a.inc_row = g->inc_row;
         a.inc_type = g->inc_type;
@@ -5903,11 +6075,10 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
         a.min_arity = o.return_source ? 1 : 2;
         a.mode = mode;
         a.rev = o.reverse_order ? 1 : 0;
-        a.kbits = ya ? 0 : kbits;   // an adjacency pair's index is its whole stream position
+        // an adjacency pair's index is its whole stream position
+        a.kbits = ya ? 0 : bitlen(g->max_arity > 1 ? (u64)(g->max_arity - 1) : 0);
         a.maxd = maxd;
         a.t_limit = std::min<int64_t>(INT32_MAX - 1, (int64_t)(0xFFFFFFFFull >> a.kbits));
-        // batches chain the grid stage behind the workgroup launches (no host round trip between the stages);
-        // a single traversal (the drop-in's next() shape) keeps its latency without the extra launch
         static const bool chain_off = ab_int("HGX_SEQ_CHAIN", 1) == 0 || ab_int("HGX_SEQ_COOP", 1) == 0;   // A/B builds
         if (!chain_off && ya && n_seeds >= kSeqChainMin && sc_fits(g)) {
             chained.reset(new ScRun(g));
@@ -5915,92 +6086,35 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
             a.chain = chained->chain_buf;
             a.chain_n = chained->chain_cnt;
         }
-        const size_t per_seed = (size_t)kSbPairs * 12 + 24;
-        int32_t* dseeds = nullptr;
-        size_t dseeds_n = 0;
-        if (n_seeds > kSbInline) {
-            dseeds_n = sizeof(int32_t) * (size_t)n_seeds;
-            dseeds = (int32_t*)g->alloc(dseeds_n);
-            int32_t* hs = (int32_t*)g->pinned_buf(dseeds_n);
-            std::memcpy(hs, seeds, dseeds_n);
-            HGX_HIP(hipMemcpyAsync(dseeds, hs, dseeds_n, hipMemcpyHostToDevice, st));
-        }
-        struct Chunk {
-            int64_t c0, nb;
-            char* h;
-        };
-        std::vector<Chunk> chunks;
+    }
+
+    // One workgroup per seed (hgx_seq_block); the seeds whose traversal outgrew it -> rerun.
+    void workgroup_stage() {
+        SbArgs a{};
+        bind_block(a);
+        SeedUpload up(g, seeds, n_seeds);
         static const bool clk_trace = trace_env("HGX_SB_CLOCK");   // per-seed start / end ticks to stderr
-        int64_t* clk = nullptr;
-        if (clk_trace) HGX_HIP(hipHostMalloc((void**)&clk, sizeof(int64_t) * 2 * (size_t)n_seeds, hipHostMallocMapped));
-        for (int64_t c0 = 0; c0 < n_seeds; c0 += kSbChunk) {
-            const int64_t nb = std::min<int64_t>(kSbChunk, n_seeds - c0);
-            PoolBuf hb = take_host_buf(g, per_seed * (size_t)nb);
-            r->hbufs.push_back(hb);
-            char* h = (char*)hb.p;
-            void* dv = nullptr;
-            HGX_HIP(hipHostGetDevicePointer(&dv, h, 0));
-            char* d = (char*)dv;
-            // layout: meta [3 nb] int64 | link [nb * kSbPairs] | atom [..] | dist [..]
-            a.n = (int32_t)nb;
-            a.c0 = (int32_t)c0;
-            a.meta = (int64_t*)d;
-            a.out_link = (int32_t*)(d + 24 * nb);
-            a.out_atom = a.out_link + nb * kSbPairs;
-            a.out_dist = a.out_atom + nb * kSbPairs;
-            if (nb <= kSbInline) {   // the kernel reads the inline seeds whenever n <= kSbInline
-                for (int64_t i = 0; i < nb; ++i) a.seed_inline[i] = seeds[c0 + i];
-                a.seeds = nullptr;
-            } else {
-                a.seeds = dseeds + c0;
-            }
-            if (clk) {
-                void* dc = nullptr;
-                HGX_HIP(hipHostGetDevicePointer(&dc, clk + 2 * c0, 0));
-                a.clk = (int64_t*)dc;
-            }
-            hgx_seq_block<<<(unsigned)nb, kSbThreads, 0, st>>>(a);
-            HGX_CHECK_LAUNCH();
-            chunks.push_back({c0, nb, h});
-        }
-        hipEvent_t evb = nullptr;
-        if (g->timing) {
-            evb = ev_take(g);
-            HGX_HIP(hipEventRecord(evb, st));
-        }
+        MappedClock clk;
+        if (clk_trace) HGX_HIP(hipHostMalloc((void**)&clk.p, sizeof(int64_t) * 2 * (size_t)n_seeds, hipHostMallocMapped));
+        const auto chunks = launch_stage_chunks(
+            g, seeds, n_seeds, kSbChunk, (size_t)kSbPairs * 12 + 24, up, r->hbufs, a, [&](int64_t c0, int64_t nb, char* d) {
+                // layout: meta [3 nb] int64 | link [nb * kSbPairs] | atom [..] | dist [..]
+                a.c0 = (int32_t)c0;
+                a.meta = (int64_t*)d;
+                a.out_link = (int32_t*)(d + 24 * nb);
+                a.out_atom = a.out_link + nb * kSbPairs;
+                a.out_dist = a.out_atom + nb * kSbPairs;
+                if (clk.p) HGX_HIP(hipHostGetDevicePointer((void**)&a.clk, clk.p + 2 * c0, 0));
+                hgx_seq_block<<<(unsigned)nb, kSbThreads, 0, st>>>(a);
+            });
+        total.mark();
         seq_mark("workgroup stage enqueued");
         if (chained) chained->launch();
         spin_sync(st);
         seq_mark("workgroup stage done");
-        if (evb) {
-            float ms = 0;
-            HGX_HIP(hipEventElapsedTime(&ms, ev0, evb));
-            r->ms_block = ms;
-            ev_give(g, evb);
-        }
-        if (dseeds) g->release(dseeds, dseeds_n);
-        if (clk) {   // per seed: start after the first start, duration (us), pairs, depth; the 12 last to end
-            int64_t t0 = INT64_MAX;
-            for (int32_t i = 0; i < n_seeds; ++i) t0 = std::min(t0, clk[2 * i]);
-            std::vector<int32_t> ord((size_t)n_seeds);
-            for (int32_t i = 0; i < n_seeds; ++i) ord[i] = i;
-            std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return clk[2 * x + 1] > clk[2 * y + 1]; });
-            double sum = 0;
-            for (int32_t i = 0; i < n_seeds; ++i) sum += (clk[2 * i + 1] - clk[2 * i]) * 0.01;
-            std::fprintf(stderr, "[hgx sb clock] seeds=%d mean_us=%.1f end_us=%.1f; last to end (seed: start/dur us, pairs, depth):",
-                         n_seeds, sum / std::max(1, n_seeds), (clk[2 * ord[0] + 1] - t0) * 0.01);
-            for (int32_t k = 0; k < std::min<int32_t>(12, n_seeds); ++k) {
-                const int32_t i = ord[k];
-                const Chunk& c = chunks[(size_t)(i / kSbChunk)];
-                const int64_t j = i - c.c0;
-                const int64_t np = ((const int64_t*)c.h)[3 * j];
-                const int32_t* ds = (const int32_t*)(c.h + 24 * c.nb) + 2 * c.nb * kSbPairs;
-                std::fprintf(stderr, " %d: %.1f/%.1f %lld %d;", i, (clk[2 * i] - t0) * 0.01, (clk[2 * i + 1] - clk[2 * i]) * 0.01,
-                             (long long)np, np > 0 ? ds[j * kSbPairs + np - 1] : 0);
-            }
-            std::fprintf(stderr, "\n");
-            (void)hipHostFree(clk);
-        }
+        if (total.on()) r->ms_block = total.ms_to_mark();
+        up.reset();
+        if (clk.p) dump_clock(clk.p, chunks);
         for (auto& c : chunks) {
             const int64_t* meta = (const int64_t*)c.h;
             const int32_t* lk_ = (const int32_t*)(c.h + 24 * c.nb);
@@ -6016,85 +6130,47 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
                 }
                 cnt[si] = np;
                 r->traversed += (double)meta[3 * i + 1];
-                r->blk[si] = {lk_ + i * kSbPairs, at + i * kSbPairs, ds + i * kSbPairs, np, 0};
+                r->blk[si] = Seg::plain(lk_ + i * kSbPairs, at + i * kSbPairs, ds + i * kSbPairs, np, 0);
                 if (np > 0) deepest = std::max(deepest, ds[i * kSbPairs + np - 1]);
             }
         }
-    } else {
-        for (int32_t i = 0; i < n_seeds; ++i) rerun.push_back(i);
     }
-    r->n_level = (int32_t)rerun.size();
-    r->n_block = n_seeds - r->n_level;
-    if (!rerun.empty()) {
-        std::vector<int32_t> rs(rerun.size());
+
+    // HGX_SB_CLOCK.  Per seed: start after the first start, duration (us), pairs, depth; the 12 last to end.
+    void dump_clock(const int64_t* clk, const std::vector<StageChunk>& chunks) const {
+        int64_t t0 = INT64_MAX;
+        for (int32_t i = 0; i < n_seeds; ++i) t0 = std::min(t0, clk[2 * i]);
+        std::vector<int32_t> ord((size_t)n_seeds);
+        for (int32_t i = 0; i < n_seeds; ++i) ord[i] = i;
+        std::sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return clk[2 * x + 1] > clk[2 * y + 1]; });
+        double sum = 0;
+        for (int32_t i = 0; i < n_seeds; ++i) sum += (clk[2 * i + 1] - clk[2 * i]) * 0.01;
+        std::fprintf(stderr, "[hgx sb clock] seeds=%d mean_us=%.1f end_us=%.1f; last to end (seed: start/dur us, pairs, depth):",
+                     n_seeds, sum / std::max(1, n_seeds), (clk[2 * ord[0] + 1] - t0) * 0.01);
+        for (int32_t k = 0; k < std::min<int32_t>(12, n_seeds); ++k) {
+            const int32_t i = ord[k];
+            const StageChunk& c = chunks[(size_t)(i / kSbChunk)];
+            const int64_t j = i - c.c0;
+            const int64_t np = ((const int64_t*)c.h)[3 * j];
+            const int32_t* ds = (const int32_t*)(c.h + 24 * c.nb) + 2 * c.nb * kSbPairs;
+            std::fprintf(stderr, " %d: %.1f/%.1f %lld %d;", i, (clk[2 * i] - t0) * 0.01, (clk[2 * i + 1] - clk[2 * i]) * 0.01,
+                         (long long)np, np > 0 ? ds[j * kSbPairs + np - 1] : 0);
+        }
+        std::fprintf(stderr, "\n");
+    }
+
+    // The seeds of rerun: the grid stage (chained, else in a launch of its own), else the level engine.
+    void later_stages() {
+        rs.resize(rerun.size());
         for (size_t k = 0; k < rerun.size(); ++k) rs[k] = seeds[rerun[k]];
-        hipEvent_t el0 = nullptr, el1 = nullptr;
-        if (g->timing) {
-            el0 = ev_take(g);
-            el1 = ev_take(g);
-            HGX_HIP(hipEventRecord(el0, st));
-        }
-        bool done = false;
-        if (chained) {   // the chained grid stage took exactly these seeds (its list, in arrival order)
-            const int64_t kk = chained->hm[5];
-            if (kk == (int64_t)rerun.size() && kk <= kMaxCoSeeds) {
-                std::vector<int32_t> pos((size_t)kk);
-                for (int64_t j = 0; j < kk; ++j) {   // list entry j -> its position in rerun (ascending)
-                    const int64_t idx = chained->hm[8 + 2 * (size_t)chained->nblk + j];
-                    const auto it = std::lower_bound(rerun.begin(), rerun.end(), (int32_t)idx);
-                    if (it == rerun.end() || *it != (int32_t)idx) fail(HGX_E_DEVICE, "hgx_bfs_sequence: chained seed list inconsistent");
-                    pos[j] = (int32_t)(it - rerun.begin());
-                }
-                SeqOut co;
-                co.segs.assign(rs.size(), {});
-                done = chained->collect((int32_t)kk, pos, co, &r->ms_coop) == 1;
-                if (done) {
-                    r->lev.segs = std::move(co.segs);
-                    r->lev.bufs = std::move(co.bufs);
-                    r->lev.traversed = co.traversed;
-                    r->lev.deepest = co.deepest;
-                    r->bytes_coop = co.bytes;
-                    r->n_coop = (int32_t)rs.size();
-                }
-            } else if (chained->hm[0] != 0 || chained->hm[3] != 0) {   // did not run them: state back to empty
-                SeqOut co;
-                (void)chained->collect(0, {}, co, &r->ms_coop);
-            }
-            chained.reset();
-        }
-        if (!done && g->seq_engine == 0 && rs.size() <= (size_t)kMaxCoSeeds) {   // the grid stage first (one launch)
-            r->lev.segs.assign(rs.size(), {});
-            std::vector<int32_t> sidx(rs.size());
-            for (size_t q = 0; q < rs.size(); ++q) sidx[q] = (int32_t)q;
-            SeqOut co;
-            co.segs.assign(rs.size(), {});
-            done = seq_coop(g, rs.data(), sidx, maxd, o, co, &r->ms_coop);
-            if (done) {
-                r->lev.segs = std::move(co.segs);
-                r->lev.bufs = std::move(co.bufs);
-                r->lev.traversed = co.traversed;
-                r->lev.deepest = co.deepest;
-                r->bytes_coop = co.bytes;
-                r->n_coop = (int32_t)rs.size();
-            } else {
-                std::lock_guard<std::mutex> lk(g->seq_mu);
-                for (auto& b : co.bufs) g->seq_hbufs.push_back(b);
-            }
-        }
+        EvTimer lt(g);
+        lt.start();
+        bool done = chained && chained_grid_stage();
+        chained.reset();
+        if (!done && g->seq_engine == 0 && rs.size() <= (size_t)kMaxCoSeeds) done = grid_stage();
         if (!done) seq_levels_all(g, rs.data(), (int32_t)rs.size(), maxd, o, r->lev, g->seq_engine != 1);
-        if (el0 && !r->lev.evs.empty()) {   // the pair copies are still running: timed on first use
-            HGX_HIP(hipEventRecord(el1, st));
-            r->lz_el0 = el0;
-            r->lz_el1 = el1;
-        } else if (el0) {
-            HGX_HIP(hipEventRecord(el1, st));
-            HGX_HIP(hipEventSynchronize(el1));
-            float ms = 0;
-            HGX_HIP(hipEventElapsedTime(&ms, el0, el1));
-            r->ms_level = ms;
-            ev_give(g, el0);
-            ev_give(g, el1);
-        }
+        // (the level engine's pair copies may still be running: then the time is read on first use)
+        lt.finish(!r->lev.evs.empty(), &r->lz_el0, &r->lz_el1, &r->ms_level);
         r->traversed += r->lev.traversed;
         deepest = std::max(deepest, r->lev.deepest);
         for (size_t k = 0; k < rerun.size(); ++k) {
@@ -6104,26 +6180,84 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
             r->lev_of[rerun[k]] = (int32_t)k;
         }
     }
-    if (g->timing && !r->lev.evs.empty()) {
-        HGX_HIP(hipEventRecord(ev1, st));
-        r->lz_ev0 = ev0;
-        r->lz_ev1 = ev1;
-    } else if (g->timing) {
-        HGX_HIP(hipEventRecord(ev1, st));
-        HGX_HIP(hipEventSynchronize(ev1));
-        seq_mark("timing event done");
-        float ms = 0;
-        HGX_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-        r->ms_total = ms;
-        ev_give(g, ev0);
-        ev_give(g, ev1);
+
+    // The chained launch has finished with the workgroup launches; true when it took exactly the seeds of rerun
+    // (its list, in arrival order) and finished them.  A launch that took another number of seeds is reset only
+    // when it did not end clean (one that ended clean left its bitmaps and tables empty); its result is not read.
+    bool chained_grid_stage() {
+        const int64_t kk = chained->seeds_taken();
+        if (kk != (int64_t)rerun.size() || kk > kMaxCoSeeds) {
+            SeqOut none;
+            if (!chained->clean()) (void)chained->collect(0, {}, none, &r->ms_coop);
+            return false;
+        }
+        std::vector<int32_t> pos((size_t)kk);
+        for (int64_t j = 0; j < kk; ++j) {   // list entry j -> its position in rerun (ascending)
+            const int32_t idx = chained->chained_index(j);
+            const auto it = std::lower_bound(rerun.begin(), rerun.end(), idx);
+            if (it == rerun.end() || *it != idx) fail(HGX_E_DEVICE, "hgx_bfs_sequence: chained seed list inconsistent");
+            pos[j] = (int32_t)(it - rerun.begin());
+        }
+        SeqOut co;
+        co.segs.assign(rs.size(), {});
+        if (chained->collect((int32_t)kk, pos, co, &r->ms_coop) != 1) return false;
+        r->adopt(std::move(co), (int32_t)rs.size());
+        return true;
     }
-    r->off.assign((size_t)n_seeds + 1, 0);
-    for (int32_t i = 0; i < n_seeds; ++i) r->off[i + 1] = r->off[i] + cnt[i];
-    r->n_levels = deepest + 1;
-    seq_mark("call done");
-    guard.r = nullptr;
-    *out = r;
+
+    // The grid stage in a launch of its own over every seed of rerun.
+    bool grid_stage() {
+        std::vector<int32_t> sidx(rs.size());
+        for (size_t q = 0; q < rs.size(); ++q) sidx[q] = (int32_t)q;
+        SeqOut co;
+        co.segs.assign(rs.size(), {});
+        if (!seq_coop(g, rs.data(), sidx, maxd, o, co, &r->ms_coop)) return false;
+        r->adopt(std::move(co), (int32_t)rs.size());
+        return true;
+    }
+
+    void finish() {
+        if (total.finish(!r->lev.evs.empty(), &r->lz_ev0, &r->lz_ev1, &r->ms_total)) seq_mark("timing event done");
+        r->off.assign((size_t)n_seeds + 1, 0);
+        for (int32_t i = 0; i < n_seeds; ++i) r->off[i + 1] = r->off[i] + cnt[i];
+        r->n_levels = deepest + 1;
+        seq_mark("call done");
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
+                     const hgx_algen_opts* opts, hgx_seq_result** out) {
+    HGX_API_BEGIN
+    if (!g || !out || n_seeds < 0 || (n_seeds > 0 && !seeds)) fail(HGX_E_INVALID, "hgx_bfs_sequence: bad argument");
+    *out = nullptr;
+    if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_bfs_sequence: not available on a partition shard");
+    // FIFO order and the discovering link follow the incidence order, i.e. rank order; after an
+    // update appended ranks whose handles may sort before existing ones that is not handle order
+    // (ADVICE r01), and no re-sort of the output can repair it.
+    if (!g->ranks_ordered)
+        fail(HGX_E_UNSUPPORTED, "hgx_bfs_sequence: ranks were appended by hgx_graph_update and may not follow "
+                                "handle order (re-assert with HGX_OPT_RANKS_ORDERED or rebuild the snapshot)");
+    const hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
+    for (int32_t i = 0; i < n_seeds; ++i)
+        if (seeds[i] < 0 || seeds[i] >= g->A) fail(HGX_E_INVALID, "hgx_bfs_sequence: seed out of range");
+    if (max_depth < -1) fail(HGX_E_INVALID, "hgx_bfs_sequence: bad max_depth");
+    std::lock_guard<std::mutex> lk(g->mu);
+    SeqTrace trace;
+    g_seq_trace = trace.on ? &trace : nullptr;
+    struct TraceOff {
+        ~TraceOff() { g_seq_trace = nullptr; }
+    } trace_off;
+    HGX_HIP(hipSetDevice(g->device));
+    std::unique_ptr<hgx_seq_result> r(new hgx_seq_result());
+    r->g = g;
+    g->refs.fetch_add(1);
+    SeqCall call(g, seeds, n_seeds, max_depth < 0 ? INT32_MAX : max_depth, o, r.get());
+    call.run();
+    *out = r.release();
     HGX_API_END
 }
 
