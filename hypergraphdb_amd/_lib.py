@@ -86,6 +86,12 @@ EXPORTED_PATHS = (
     "hgx_sp_result_stats", "hgx_sp_result_free",
 )
 
+# Every symbol include/hgx_linkpred.h declares (checked by tests/test_linkpred_ref.py without a GPU).
+EXPORTED_LINKPRED = (
+    "hgx_link_predicate_create", "hgx_link_predicate_free", "hgx_link_predicate_info", "hgx_link_predicate_flags",
+    "hgx_bfs_batch_pred", "hgx_bfs_sequence_pred", "hgx_shortest_paths_pred",
+)
+
 # Every symbol include/hgx_dnf.h declares (checked by tests/test_dnf_ref.py without a GPU).
 EXPORTED_DNF = ("hgx_pattern_batch_dnf", "hgx_query_result_union_stats")
 
@@ -302,6 +308,15 @@ def lib():
         "hgx_hop_paths_free": ([vp], None),
         "hgx_bfs_result_depth_row": ([vp, i32, i64, i64, vp], C.c_int),
         "hgx_bfs_result_predecessor_row": ([vp, i32, i64, i64, vp, vp], C.c_int),
+        # include/hgx_linkpred.h
+        "hgx_link_predicate_create": ([vp, i64, vp, vp, vp, i64, C.POINTER(vp)], C.c_int),
+        "hgx_link_predicate_free": ([vp], None),
+        "hgx_link_predicate_info": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double)], C.c_int),
+        "hgx_link_predicate_flags": ([vp, i64, i64, vp], C.c_int),
+        "hgx_bfs_batch_pred": ([vp, vp, i32, i32, C.POINTER(AlgenOpts), vp, C.POINTER(vp)], C.c_int),
+        "hgx_bfs_sequence_pred": ([vp, vp, i32, i32, C.POINTER(AlgenOpts), vp, C.POINTER(vp)], C.c_int),
+        "hgx_shortest_paths_pred": ([vp, vp, vp, i32, C.POINTER(AlgenOpts), vp, vp, C.POINTER(vp)], C.c_int),
     }
     for name, (args, res) in sig.items():
         if LIB_VARIANT and not hasattr(L, name):

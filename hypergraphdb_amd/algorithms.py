@@ -40,9 +40,96 @@ class AtomTypeCondition:
         return f"type({self.type})"
 
 
+class LinkPredicate:
+    """A link predicate of a DefaultALGenerator, evaluated once per link row on the snapshot's device
+    (hgx_link_predicate, include/hgx_linkpred.h): any tree of hg.and_ / hg.or_ / hg.not_ over the accelerated
+    leaves -- type, typePlus, incident, incidentAt / incidentNotAt, orderedLink, link, arity.  Anything else in
+    the tree raises HGXUnsupported.  Reusable across calls and across the snapshot's contexts; a result made
+    with it keeps it alive, so closing it first is fine.  While one lives the snapshot refuses updates."""
+
+    def __init__(self, snapshot, cond):
+        self._h = None
+        lit_off, lit, ops = encode_link_predicate(lower_link_predicate(cond))
+        h = C.c_void_p()
+        check(lib().hgx_link_predicate_create(snapshot.handle, len(lit_off) - 1, ptr(lit_off), ptr(lit), ptr(ops),
+                                              len(ops), C.byref(h)))
+        self._h = h
+        self.snapshot = snapshot
+        self.cond = cond
+        self.num_links, self.num_satisfied, self._ms, self._bytes = self._info()
+
+    def _info(self):
+        m, ns, ms, by = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+        check(lib().hgx_link_predicate_info(self.handle, C.byref(m), C.byref(ns), C.byref(ms), C.byref(by)))
+        return m.value, ns.value, ms.value, by.value
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("link predicate closed")
+        return self._h
+
+    def flags(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """uint8 per link row of [first, first + n): 1 = the row satisfies the predicate."""
+        n = self.num_links - first if n is None else n
+        out = np.empty(max(n, 1), np.uint8)
+        check(lib().hgx_link_predicate_flags(self.handle, int(first), int(n), ptr(out) if n else None))
+        return out[:n]
+
+    def stats(self) -> dict:
+        """Device ms of the evaluation and projection kernels (timing enabled) and their algorithmic bytes."""
+        return {"num_links": self.num_links, "num_satisfied": self.num_satisfied, "ms_eval": self._ms,
+                "bytes_eval": self._bytes}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().hgx_link_predicate_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lower_link_predicate(cond):
+    """A condition tree -> the terms of its disjunctive normal form, tuples of (leaf, polarity) literals: the
+    lowering of a negated tree (query.lower_not) applied to the tree itself, without the outer Not."""
+    from .query import Not, lower_not   # (query imports this module)
+    return lower_not(Not(cond))
+
+
+def encode_link_predicate(terms):
+    """terms -> (lit_off, lit, ops) of hgx_link_predicate_create."""
+    from .query import _literal
+    lit_off, lit, ops = [0], [], []
+    for term in terms:
+        for leaf, pol in term:
+            kind, operands = _literal(leaf)
+            lit.extend((kind, int(bool(pol)), len(ops), len(ops) + len(operands)))
+            ops.extend(operands)
+        lit_off.append(len(lit) // 4)
+    return np.array(lit_off, np.int64), np.array(lit, np.int32), np.array(ops, np.int32)
+
+
+def decode_link_predicate(lit_off, lit, ops):
+    """The inverse of encode_link_predicate up to the leaf classes: (kind, polarity, operand tuple) literals."""
+    return [[(int(lit[4 * l]), int(lit[4 * l + 1]), tuple(int(x) for x in ops[lit[4 * l + 2]:lit[4 * l + 3]]))
+             for l in range(lit_off[t], lit_off[t + 1])] for t in range(len(lit_off) - 1)]
+
+
 class DefaultALGenerator:
-    """Adjacency-list generator configuration.  Only linkPredicate in {None, AtomTypeCondition}
-    and siblingPredicate None are accelerated (any other predicate: HGXUnsupported)."""
+    """Adjacency-list generator configuration.  linkPredicate: None, an AtomTypeCondition (both through the
+    type key of hgx_algen_opts), a LinkPredicate, or a raw tree of hg.and_ / hg.or_ / hg.not_ over the
+    accelerated leaves, which every call compiles into a LinkPredicate of its own and releases when it returns
+    (include/hgx_linkpred.h).  A siblingPredicate is not accelerated (HGXUnsupported)."""
 
     def __init__(self, graph, link_predicate=None, sibling_predicate=None, return_preceding=True,
                  return_succeeding=True, reverse_order=False, return_source=None):
@@ -71,6 +158,21 @@ class DefaultALGenerator:
             raise _lib.HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"link predicate {self.link_predicate!r}")
         return _lib.AlgenOpts(lt, int(self.return_preceding), int(self.return_succeeding),
                               int(self.reverse_order), int(self.return_source))
+
+    def compiled(self, snapshot):
+        """(options, LinkPredicate or None, owned): what a traversal call hands to the engine.  None and an
+        AtomTypeCondition go through ``options()``; a LinkPredicate is used as it is; any other tree is
+        compiled now (owned = True: the caller closes it when its call returns)."""
+        lp = self.link_predicate
+        if lp is None or isinstance(lp, AtomTypeCondition):
+            return self.options(), None, False
+        if self.sibling_predicate is not None:
+            raise _lib.HGXUnsupported(_lib.HGX_E_UNSUPPORTED, "siblingPredicate is not accelerated")
+        opts = _lib.AlgenOpts(_lib.HGX_NO_TYPE, int(self.return_preceding), int(self.return_succeeding),
+                              int(self.reverse_order), int(self.return_source))
+        if isinstance(lp, LinkPredicate):
+            return opts, lp, False
+        return opts, LinkPredicate(snapshot, lp), True
 
 
 class BfsResult:
@@ -235,11 +337,18 @@ class HopPaths:
 def bfs_batch(snapshot, seeds, max_depth=None, generator: DefaultALGenerator | None = None) -> BfsResult:
     """HGBreadthFirstTraversal(seeds[i], generator, max_depth) for every i, run together on the GPU."""
     gen = generator or DefaultALGenerator(snapshot)
-    opts = gen.options()
+    opts, pred, owned = gen.compiled(snapshot)
     s = np.ascontiguousarray(seeds, np.int32)
     md = _lib.HGX_UNBOUNDED if max_depth is None or max_depth >= 2**31 - 1 else int(max_depth)
     h = C.c_void_p()
-    check(lib().hgx_bfs_batch(snapshot.handle, ptr(s), len(s), md, C.byref(opts), C.byref(h)))
+    try:
+        if pred is None:
+            check(lib().hgx_bfs_batch(snapshot.handle, ptr(s), len(s), md, C.byref(opts), C.byref(h)))
+        else:
+            check(lib().hgx_bfs_batch_pred(snapshot.handle, ptr(s), len(s), md, C.byref(opts), pred.handle, C.byref(h)))
+    finally:
+        if owned:
+            pred.close()   # the result holds its own reference
     return BfsResult(snapshot, h, s)
 
 
@@ -290,11 +399,19 @@ def bfs_sequence(snapshot, seeds, max_depth=None, generator: DefaultALGenerator 
     """The exact next() sequence of HGBreadthFirstTraversal(seeds[i], generator, max_depth) for
     every i (FIFO order and discovering links as in the reference), computed on the GPU."""
     gen = generator or DefaultALGenerator(snapshot)
-    opts = gen.options()
+    opts, pred, owned = gen.compiled(snapshot)
     s = np.ascontiguousarray(seeds, np.int32)
     md = _lib.HGX_UNBOUNDED if max_depth is None or max_depth >= 2**31 - 1 else int(max_depth)
     h = C.c_void_p()
-    check(lib().hgx_bfs_sequence(snapshot.handle, ptr(s), len(s), md, C.byref(opts), C.byref(h)))
+    try:
+        if pred is None:
+            check(lib().hgx_bfs_sequence(snapshot.handle, ptr(s), len(s), md, C.byref(opts), C.byref(h)))
+        else:
+            check(lib().hgx_bfs_sequence_pred(snapshot.handle, ptr(s), len(s), md, C.byref(opts), pred.handle,
+                                              C.byref(h)))
+    finally:
+        if owned:
+            pred.close()
     return SequenceResult(h, s)
 
 

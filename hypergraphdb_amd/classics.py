@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .algorithms import DefaultALGenerator, HopPaths, bfs_batch
+from .algorithms import DefaultALGenerator, HopPaths, LinkPredicate, bfs_batch  # noqa: F401
 
 NO_GOAL = _lib.HGX_NO_GOAL
 
@@ -148,7 +148,6 @@ def shortest_paths(snapshot, starts, goals, generator: DefaultALGenerator | None
     None (1.0 per link), an array with one value per link row, a LinkWeights, or a callable
     link atom -> float (evaluated once per link)."""
     gen = generator or DefaultALGenerator(snapshot)
-    opts = gen.options()
     s = np.ascontiguousarray(starts, np.int32)
     g = np.ascontiguousarray([NO_GOAL if x is None else int(x) for x in goals], np.int32)
     if s.shape != g.shape or s.ndim != 1:
@@ -161,12 +160,20 @@ def shortest_paths(snapshot, starts, goals, generator: DefaultALGenerator | None
     else:
         own = LinkWeights.from_mapping(snapshot, weights) if callable(weights) else LinkWeights(snapshot, weights)
         wh = own.handle
+    pred, owned = None, False
     try:
+        opts, pred, owned = gen.compiled(snapshot)
         h = C.c_void_p()
-        check(lib().hgx_shortest_paths(snapshot.handle, ptr(s), ptr(g), len(s), C.byref(opts), wh, C.byref(h)))
+        if pred is None:
+            check(lib().hgx_shortest_paths(snapshot.handle, ptr(s), ptr(g), len(s), C.byref(opts), wh, C.byref(h)))
+        else:
+            check(lib().hgx_shortest_paths_pred(snapshot.handle, ptr(s), ptr(g), len(s), C.byref(opts), wh,
+                                                pred.handle, C.byref(h)))
     finally:
         if own is not None:
             own.close()
+        if owned:
+            pred.close()   # the result holds its own reference
     return ShortestPathsResult(snapshot, h, s, g)
 
 

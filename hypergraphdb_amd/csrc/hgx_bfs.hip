@@ -5868,7 +5868,24 @@ void ensure_accounting(hgx_bfs_result* r) {
 }
 
 void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
-                    const hgx_algen_opts* opts, hgx_bfs_result** out);
+                    const hgx_algen_opts* opts, hgx_bfs_result** out, hgx_link_predicate* pred = nullptr);
+
+// hgx_bfs_batch and hgx_bfs_batch_pred (pred null: the former)
+void bfs_batch_entry(const char* who, hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
+                     const hgx_algen_opts* opts, hgx_link_predicate* pred, hgx_bfs_result** out) {
+    const std::string w(who);
+    if (!g || !out || n_seeds < 0 || (n_seeds > 0 && !seeds)) fail(HGX_E_INVALID, w + ": bad argument");
+    *out = nullptr;
+    if (g->shard) {
+        if (pred) fail(HGX_E_UNSUPPORTED, w + ": not available on a partition shard");
+        fail(HGX_E_INVALID, w + ": a partition shard needs hgx_pbfs_batch (a transport)");
+    }
+    if (pred) pred_check(g, pred, opts, who);
+    for (int32_t i = 0; i < n_seeds; ++i)
+        if (seeds[i] < 0 || seeds[i] >= g->A) fail(HGX_E_INVALID, w + ": seed out of range");
+    if (max_depth < -1) fail(HGX_E_INVALID, w + ": bad max_depth");
+    bfs_batch_impl(g, nullptr, seeds, n_seeds, max_depth, opts, out, pred);
+}
 
 }  // namespace
 
@@ -5877,13 +5894,14 @@ extern "C" {
 int hgx_bfs_batch(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
                   const hgx_algen_opts* opts, hgx_bfs_result** out) {
     HGX_API_BEGIN
-    if (!g || !out || n_seeds < 0 || (n_seeds > 0 && !seeds)) fail(HGX_E_INVALID, "hgx_bfs_batch: bad argument");
-    *out = nullptr;
-    if (g->shard) fail(HGX_E_INVALID, "hgx_bfs_batch: a partition shard needs hgx_pbfs_batch (a transport)");
-    for (int32_t i = 0; i < n_seeds; ++i)
-        if (seeds[i] < 0 || seeds[i] >= g->A) fail(HGX_E_INVALID, "hgx_bfs_batch: seed out of range");
-    if (max_depth < -1) fail(HGX_E_INVALID, "hgx_bfs_batch: bad max_depth");
-    bfs_batch_impl(g, nullptr, seeds, n_seeds, max_depth, opts, out);
+    bfs_batch_entry("hgx_bfs_batch", g, seeds, n_seeds, max_depth, opts, nullptr, out);
+    HGX_API_END
+}
+
+int hgx_bfs_batch_pred(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
+                       const hgx_algen_opts* opts, hgx_link_predicate* p, hgx_bfs_result** out) {
+    HGX_API_BEGIN
+    bfs_batch_entry(p ? "hgx_bfs_batch_pred" : "hgx_bfs_batch", g, seeds, n_seeds, max_depth, opts, p, out);
     HGX_API_END
 }
 
@@ -6032,10 +6050,12 @@ void account_level(hgx_bfs_result* r, const BfsBatch& bt, int mode, int d, const
 }
 
 void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
-                    const hgx_algen_opts* opts, hgx_bfs_result** out) {
+                    const hgx_algen_opts* opts, hgx_bfs_result** out, hgx_link_predicate* pred) {
     hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
+    if (pred) o.link_type = kLinkPredKey;   // the typed generator over the predicate's flags
     const ShardInfo* shp = g->shard;
     std::lock_guard<std::mutex> lk(g->mu);
+    PredScope pred_scope(g, pred);
     HGX_HIP(hipSetDevice(g->device));
     const int mode = mode_of(o);
 
@@ -6054,11 +6074,13 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
             }
             if (r->blk) block_release(r->g, *r->blk);
             r->g->refs.fetch_sub(1);   // the caller still holds its own reference
+            pred_release(r->pred);     // (likewise)
             delete r;
         }
     } guard{r};
     r->g = g;
     g->refs.fetch_add(1);
+    r->pred = pred_ref(pred);
     r->n_seeds = n_seeds;
     r->typed = o.link_type >= 0;
     r->opts = o;
@@ -6347,7 +6369,9 @@ void hgx_bfs_result_free(hgx_bfs_result* r) {
         if (r->hop_depth) g->release(r->hop_depth, sizeof(int32_t) * (size_t)std::max<int64_t>(g->A, 1));
         if (r->hop_key) g->release(r->hop_key, sizeof(u64) * (size_t)std::max<int64_t>(g->A, 1));
     }
+    hgx_link_predicate* const pred = r->pred;
     delete r;
+    pred_release(pred);
     if (g) graph_release(g);
 }
 

@@ -36,8 +36,15 @@ void graph_release(hgx_graph* g) {
     hgx_graph* const b = g->base;
 #define HGX_FREE_OWN(f) \
     if (g->f && (!b || (const void*)g->f != (const void*)b->f)) (void)hipFree(g->f)
-    HGX_FREE_OWN(link_atom); HGX_FREE_OWN(tgt_off); HGX_FREE_OWN(tgt_idx); HGX_FREE_OWN(link_type);
-    HGX_FREE_OWN(inc_off); HGX_FREE_OWN(inc_row); HGX_FREE_OWN(inc_type); HGX_FREE_OWN(inc_ts_row);
+    HGX_FREE_OWN(link_atom); HGX_FREE_OWN(tgt_off); HGX_FREE_OWN(tgt_idx);
+    HGX_FREE_OWN(inc_off); HGX_FREE_OWN(inc_row); HGX_FREE_OWN(inc_ts_row);
+    // link_type / inc_type: a context always borrows them, and no comparison with the base's fields decides it --
+    // while a link predicate's traversal runs on the base (PredScope) those point at the predicate's flags, and
+    // this release takes no lock
+    if (!b) {
+        if (g->link_type) (void)hipFree(g->link_type);
+        if (g->inc_type) (void)hipFree(g->inc_type);
+    }
     HGX_FREE_OWN(inc_ts_type); HGX_FREE_OWN(inc_ts_tgt); HGX_FREE_OWN(heavy_atom); HGX_FREE_OWN(chunks);
     HGX_FREE_OWN(hasinc); HGX_FREE_OWN(nbr_hint); HGX_FREE_OWN(top_list); HGX_FREE_OWN(inc_yf); HGX_FREE_OWN(pchunks); HGX_FREE_OWN(type_idx);
 #undef HGX_FREE_OWN

@@ -380,7 +380,7 @@ HopGraph graph_args(const hgx_bfs_result* r) {
     a.want_type = r->opts.link_type >= 0 ? r->opts.link_type : -1;
     a.inc_off = g->inc_off;
     a.inc_row = g->inc_row;
-    a.inc_type = g->inc_type;
+    a.inc_type = r->pred ? r->pred->inc_flag : g->inc_type;   // (want_type is then the predicate key)
     a.tgt_off = g->tgt_off;
     a.tgt_idx = g->tgt_idx;
     a.link_atom = g->link_atom;

@@ -28,6 +28,7 @@
 #include "../../include/hgx_dnf.h"
 #include "../../include/hgx_hops.h"
 #include "../../include/hgx_join.h"
+#include "../../include/hgx_linkpred.h"
 #include "../../include/hgx_not.h"
 #include "../../include/hgx_paths.h"
 #include "../../include/hgx_scan.h"
@@ -317,6 +318,7 @@ struct hgx_graph {
     int64_t co_timeouts = 0;                        //   launches whose grid barrier timed out (seeds fell back)
     int32_t sc_ok = -1;                             // order-exact grid stage (hgx_seq_coop): its grid (0: does not fit)
     int64_t sc_pcap = 0;                            //   its pair capacity (grown on demand)
+    hgx_link_predicate* pred = nullptr;             // the link predicate of the traversal in progress (PredScope; under mu)
     std::deque<hgx::YieldList> ylists;              // yield lists (snapshot only; contexts read their base's)
     std::deque<hgx::YieldAdj> yadjs;                // yield adjacencies (likewise)
     std::mutex ylist_mu;
@@ -401,7 +403,53 @@ struct hgx_graph {
     void* zc_in_buf(size_t bytes);   // host pointer; zc_in_dev is the kernels' view of it
 };
 
+// A link predicate (include/hgx_linkpred.h, hgx_linkpred.hip): its flags per link row and per incidence entry
+// as int32 arrays, so that a traversal reads them in place of link_type / inc_type with the type key 1, and the
+// per-(mode, type) lists the engines build over those arrays -- kept here, not on the snapshot, so they are keyed
+// apart from every real type and every other predicate, and are freed with it.
+struct hgx_link_predicate {
+    hgx_graph* root = nullptr;       // the snapshot (a reference is held)
+    std::atomic<int> refs{1};        // the caller's handle + one per result made with it
+    int64_t M = 0, I = 0, n_sat = 0;
+    int32_t* flag = nullptr;         // [M] 1 = the link row satisfies the predicate
+    int32_t* inc_flag = nullptr;     // [I] flag[inc_row[i]]
+    double ms_eval = 0, bytes_eval = 0;
+    std::deque<hgx::YieldList> ylists;   // guarded by root->ylist_mu
+    std::deque<hgx::YieldAdj> yadjs;
+};
+
 namespace hgx {
+// A reference for a result (p may be null) / dropping one: the last frees the arrays, the lists and the
+// predicate's reference on its snapshot.  Neither needs a graph mutex.
+inline hgx_link_predicate* pred_ref(hgx_link_predicate* p) {
+    if (p) p->refs.fetch_add(1);
+    return p;
+}
+void pred_release(hgx_link_predicate* p);
+// The argument checks of the *_pred entry points (p not null): p belongs to g's snapshot, opts carries no type.
+void pred_check(const hgx_graph* g, const hgx_link_predicate* p, const hgx_algen_opts* opts, const char* who);
+// While alive, g's traversal code sees p's flags as link_type / inc_type and p's lists as the yield lists
+// (p null: nothing changes).  The caller holds g->mu and passes the type key kLinkPredKey to the engines.
+// Only code that holds g->mu may read g->link_type / g->inc_type (hgx_graph_context copies them under the
+// snapshot's mutex; graph_release, which takes no lock, does not look at them for a context).
+constexpr int32_t kLinkPredKey = 1;
+struct PredScope {
+    hgx_graph* g;
+    int32_t *lt, *it;
+    PredScope(hgx_graph* gg, hgx_link_predicate* p) : g(gg), lt(gg->link_type), it(gg->inc_type) {
+        if (!p) return;
+        g->link_type = p->flag;
+        g->inc_type = p->inc_flag;
+        g->pred = p;
+    }
+    ~PredScope() {
+        g->link_type = lt;
+        g->inc_type = it;
+        g->pred = nullptr;
+    }
+    PredScope(const PredScope&) = delete;
+    PredScope& operator=(const PredScope&) = delete;
+};
 void graph_release(hgx_graph* g);
 void free_yield_lists(hgx_graph* g);   // (hgx_graph_update: the incidence changed)   // drop a reference; frees at zero
 // Builds the BFS's first-use read-only tables (has-incidence bitmap, yield flags, push chunks) on g
@@ -601,6 +649,13 @@ struct NotProgram {
 // Every offset, operand range, atom id and kind of the program, on the host (hgx_not.hip): fails with
 // HGX_E_INVALID / HGX_E_UNSUPPORTED naming the query, the clause and the negation.  A = atoms of the graph.
 void not_validate(int64_t A, int32_t n_queries, const int64_t* clause_off, NotProgram& p);
+// The checks of literal l alone (operand range, operand count, atom ids, kind, limits): 0, or the status with the
+// reason in why -- the caller puts the place in front of it.  Shared by not_validate and linkpred_validate.
+int not_check_literal(int64_t A, const NotProgram& p, int64_t l, std::string& why);
+// The same checks for a link predicate (include/hgx_linkpred.h): one tree in disjunctive normal form, n_terms
+// terms; fills p.n_terms / p.n_lits and tells whether a literal reads targets.  Messages name the term and the
+// literal.
+void linkpred_validate(int64_t A, int64_t n_terms, NotProgram& p, bool* needs_targets);
 // Its device copy (neg_off == nullptr: the batch has no negation).
 struct NotDev {
     const int64_t* neg_off = nullptr;
@@ -723,6 +778,7 @@ struct hgx_bfs_result {
     bool counts_ready = false, accounting_ready = false;
     bool typed = false;
     hgx_algen_opts opts{HGX_NO_TYPE, 1, 1, 0, 0};   // the generator the result was made with (hgx_hops.h readers)
+    hgx_link_predicate* pred = nullptr;             // its link predicate (a reference; opts.link_type is then kLinkPredKey)
     std::map<int32_t, int32_t> isolated;   // shards: seed index -> owned seed atom without incidence
     std::vector<int64_t> counts;   // [n_seeds * n_levels]
     // Seeds finished by the workgroup engine (HGX_OPT_BFS_BLOCK); the batches then hold only the

@@ -92,6 +92,50 @@ std::string where(int32_t n_queries, const int64_t* clause_off, int64_t c, int64
 
 }  // namespace
 
+int not_check_literal(int64_t A, const NotProgram& p, int64_t l, std::string& why) {
+    const int32_t kind = p.lit[4 * l], b = p.lit[4 * l + 2], e = p.lit[4 * l + 3];
+    if (b < 0 || e < b || e > p.n_ops) return why = ": operand range outside ops", HGX_E_INVALID;
+    const int32_t m = e - b;
+    const int32_t* op = p.ops + b;
+    auto bad_atom = [&](int32_t h) { return h < 0 || h >= A; };
+    const char* const range = ": atom id out of range";
+    const char* const limits = " exceeds the condition limits";
+    switch (kind) {
+    case HGX_NOT_TYPE:
+        if (m > kNotMaxTypes) return why = limits, HGX_E_UNSUPPORTED;
+        for (int32_t i = 0; i < m; ++i)
+            if (op[i] < 0) return why = ": bad type", HGX_E_INVALID;
+        break;
+    case HGX_NOT_INCIDENT:
+        if (m != 1) return why = ": an incident literal has one operand", HGX_E_INVALID;
+        if (bad_atom(op[0])) return why = range, HGX_E_INVALID;
+        break;
+    case HGX_NOT_POSITIONED:
+        if (m != 4) return why = ": a positioned literal has four operands", HGX_E_INVALID;
+        if (bad_atom(op[0])) return why = range, HGX_E_INVALID;
+        break;
+    case HGX_NOT_ORDERED:
+        if (m > kNotMaxOperands) return why = limits, HGX_E_UNSUPPORTED;
+        for (int32_t i = 0; i < m; ++i)
+            if (op[i] != HGX_ANY_HANDLE && bad_atom(op[i])) return why = range, HGX_E_INVALID;
+        break;
+    case HGX_NOT_LINK:
+        if (m > kNotMaxOperands) return why = limits, HGX_E_UNSUPPORTED;
+        for (int32_t i = 0; i < m; ++i) {
+            if (op[i] != HGX_ANY_HANDLE && bad_atom(op[i])) return why = range, HGX_E_INVALID;
+            for (int32_t k = 0; k < i; ++k)
+                if (op[k] == op[i]) return why = ": a link set repeats a member", HGX_E_INVALID;
+        }
+        break;
+    case HGX_NOT_ARITY:
+        if (m != 1 || op[0] < 0) return why = ": bad arity literal", HGX_E_INVALID;
+        break;
+    default:
+        return why = ": unknown literal kind " + std::to_string(kind), HGX_E_INVALID;
+    }
+    return HGX_OK;
+}
+
 void not_validate(int64_t A, int32_t n_queries, const int64_t* clause_off, NotProgram& p) {
     const char* who = "hgx_pattern_batch_dnf_not: ";
     const int64_t nc = clause_off[n_queries];
@@ -129,47 +173,9 @@ void not_validate(int64_t A, int32_t n_queries, const int64_t* clause_off, NotPr
         for (int64_t g = p.neg_off[c]; g < p.neg_off[c + 1]; ++g)
             for (int64_t t = p.term_off[g]; t < p.term_off[g + 1]; ++t)
                 for (int64_t l = p.lit_off[t]; l < p.lit_off[t + 1]; ++l) {
-                    auto at = [&] { return where(n_queries, clause_off, c, g - p.neg_off[c]); };   // error paths only
-                    const int32_t kind = p.lit[4 * l], b = p.lit[4 * l + 2], e = p.lit[4 * l + 3];
-                    if (b < 0 || e < b || e > p.n_ops) fail(HGX_E_INVALID, at() + ": operand range outside ops");
-                    const int32_t m = e - b;
-                    const int32_t* op = p.ops + b;
-                    auto atom = [&](int32_t h) {
-                        if (h < 0 || h >= A) fail(HGX_E_INVALID, at() + ": atom id out of range");
-                    };
-                    switch (kind) {
-                    case HGX_NOT_TYPE:
-                        if (m > kNotMaxTypes) fail(HGX_E_UNSUPPORTED, at() + " exceeds the condition limits");
-                        for (int32_t i = 0; i < m; ++i)
-                            if (op[i] < 0) fail(HGX_E_INVALID, at() + ": bad type");
-                        break;
-                    case HGX_NOT_INCIDENT:
-                        if (m != 1) fail(HGX_E_INVALID, at() + ": an incident literal has one operand");
-                        atom(op[0]);
-                        break;
-                    case HGX_NOT_POSITIONED:
-                        if (m != 4) fail(HGX_E_INVALID, at() + ": a positioned literal has four operands");
-                        atom(op[0]);
-                        break;
-                    case HGX_NOT_ORDERED:
-                        if (m > kNotMaxOperands) fail(HGX_E_UNSUPPORTED, at() + " exceeds the condition limits");
-                        for (int32_t i = 0; i < m; ++i)
-                            if (op[i] != HGX_ANY_HANDLE) atom(op[i]);
-                        break;
-                    case HGX_NOT_LINK:
-                        if (m > kNotMaxOperands) fail(HGX_E_UNSUPPORTED, at() + " exceeds the condition limits");
-                        for (int32_t i = 0; i < m; ++i) {
-                            if (op[i] != HGX_ANY_HANDLE) atom(op[i]);
-                            for (int32_t k = 0; k < i; ++k)
-                                if (op[k] == op[i]) fail(HGX_E_INVALID, at() + ": a link set repeats a member");
-                        }
-                        break;
-                    case HGX_NOT_ARITY:
-                        if (m != 1 || op[0] < 0) fail(HGX_E_INVALID, at() + ": bad arity literal");
-                        break;
-                    default:
-                        fail(HGX_E_INVALID, at() + ": unknown literal kind " + std::to_string(kind));
-                    }
+                    std::string why;
+                    if (const int rc = not_check_literal(A, p, l, why))
+                        fail(rc, where(n_queries, clause_off, c, g - p.neg_off[c]) + why);
                 }
 }
 

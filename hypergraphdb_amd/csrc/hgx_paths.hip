@@ -364,6 +364,8 @@ struct hgx_link_weights {
 
 struct hgx_sp_result {
     hgx_graph* g = nullptr;
+    hgx_link_predicate* pred = nullptr;   // the link predicate it was made with: a reference, kept for the lifetime rule
+                                          // only (include/hgx_linkpred.h); no reader of this result uses it
     int32_t n_pairs = 0;
     int64_t A = 0;
     std::vector<int32_t> goals;
@@ -659,20 +661,28 @@ void hgx_link_weights_free(hgx_link_weights* w) {
 
 int hgx_shortest_paths(hgx_graph* g, const int32_t* starts, const int32_t* goals, int32_t n_pairs,
                        const hgx_algen_opts* opts, const hgx_link_weights* w, hgx_sp_result** out) {
+    return hgx_shortest_paths_pred(g, starts, goals, n_pairs, opts, w, nullptr, out);
+}
+
+int hgx_shortest_paths_pred(hgx_graph* g, const int32_t* starts, const int32_t* goals, int32_t n_pairs,
+                            const hgx_algen_opts* opts, const hgx_link_weights* w, hgx_link_predicate* p,
+                            hgx_sp_result** out) {
     HGX_API_BEGIN
-    if (!g || !out || n_pairs < 0 || (n_pairs > 0 && (!starts || !goals)))
-        fail(HGX_E_INVALID, "hgx_shortest_paths: bad argument");
+    const std::string who = p ? "hgx_shortest_paths_pred" : "hgx_shortest_paths";
+    if (!g || !out || n_pairs < 0 || (n_pairs > 0 && (!starts || !goals))) fail(HGX_E_INVALID, who + ": bad argument");
     *out = nullptr;
-    if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_shortest_paths: not available on a partition shard");
-    const hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
+    if (g->shard) fail(HGX_E_UNSUPPORTED, who + ": not available on a partition shard");
+    if (p) pred_check(g, p, opts, who.c_str());
+    hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
+    if (p) o.link_type = kLinkPredKey;   // the typed generator over the predicate's flags
     std::lock_guard<std::mutex> lk(g->mu);
+    PredScope pred_scope(g, p);
     for (int32_t i = 0; i < n_pairs; ++i) {
-        if (starts[i] < 0 || starts[i] >= g->A) fail(HGX_E_INVALID, "hgx_shortest_paths: start out of range");
-        if (goals[i] != HGX_NO_GOAL && (goals[i] < 0 || goals[i] >= g->A))
-            fail(HGX_E_INVALID, "hgx_shortest_paths: goal out of range");
+        if (starts[i] < 0 || starts[i] >= g->A) fail(HGX_E_INVALID, who + ": start out of range");
+        if (goals[i] != HGX_NO_GOAL && (goals[i] < 0 || goals[i] >= g->A)) fail(HGX_E_INVALID, who + ": goal out of range");
     }
     if (w && (w->M != g->M || w->device != g->device))
-        fail(HGX_E_INVALID, "hgx_shortest_paths: the weights were made for another link count or device");
+        fail(HGX_E_INVALID, who + ": the weights were made for another link count or device");
     HGX_HIP(hipSetDevice(g->device));
     hgx_sp_result* r = new hgx_sp_result();
     struct Guard {   // error path: the graph mutex is held here, so release without re-locking
@@ -682,11 +692,13 @@ int hgx_shortest_paths(hgx_graph* g, const int32_t* starts, const int32_t* goals
             (void)hipStreamSynchronize(r->g->stream);
             release_rows(r);
             r->g->refs.fetch_sub(1);   // the caller still holds its own reference
+            pred_release(r->pred);     // (likewise)
             delete r;
         }
     } guard{r};
     r->g = g;
     g->refs.fetch_add(1);
+    r->pred = pred_ref(p);
     r->n_pairs = n_pairs;
     r->A = g->A;
     r->goals.assign(goals, goals + n_pairs);
@@ -787,7 +799,9 @@ void hgx_sp_result_free(hgx_sp_result* r) {
         (void)hipSetDevice(g->device);
         release_rows(r);
     }
+    hgx_link_predicate* const pred = r->pred;
     delete r;
+    pred_release(pred);
     if (g) graph_release(g);
 }
 

@@ -5823,10 +5823,13 @@ const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arit
     if (mode == kSym && type < 0) return nullptr;   // every co-target of every entry: too large to keep
     hgx_graph* root = g->base ? g->base : g;         // built once on the snapshot, read by its contexts
     std::lock_guard<std::mutex> lk(root->ylist_mu);
-    for (const YieldAdj& y : root->yadjs)
+    // a link predicate's traversal (PredScope): inc_type holds its flags, so the adjacency is the predicate's
+    // own -- kept on it, apart from every real type and every other predicate, and freed with it
+    std::deque<YieldAdj>& yadjs = g->pred ? g->pred->yadjs : root->yadjs;
+    for (const YieldAdj& y : yadjs)
         if (y.mode == mode && y.type == type && y.min_arity == min_arity && y.rev == (int32_t)rev)
             return y.off ? &y : nullptr;
-    if (root->yadjs.size() >= kMaxYieldLists) return nullptr;
+    if (yadjs.size() >= kMaxYieldLists) return nullptr;
     if (mode != kSym) ensure_inc_yield(g);
     hipStream_t st = g->stream;
     const int64_t A = g->A;
@@ -5853,7 +5856,7 @@ const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arit
     });
     if (y.n * 8 > kYieldAdjBudget) {   // remembered as refused: the yield list serves instead
         HGX_HIP(hipFree(off));
-        root->yadjs.push_back(y);
+        yadjs.push_back(y);
         return nullptr;
     }
     y.off = off;
@@ -5865,17 +5868,18 @@ const YieldAdj* yield_adj(hgx_graph* g, int mode, int32_t type, int32_t min_arit
     hgx_ya_fill<<<grid, 256, 0, st>>>(a);
     HGX_CHECK_LAUNCH();
     HGX_HIP(hipStreamSynchronize(st));
-    root->yadjs.push_back(y);
-    return &root->yadjs.back();
+    yadjs.push_back(y);
+    return &yadjs.back();
 }
 
 const YieldList* yield_list(hgx_graph* g, int mode, int32_t type) {
     if (mode == kSym && type < 0) return nullptr;   // every entry: the incidence itself
     hgx_graph* root = g->base ? g->base : g;         // built once on the snapshot, read by its contexts
     std::lock_guard<std::mutex> lk(root->ylist_mu);
-    for (const YieldList& y : root->ylists)
+    std::deque<YieldList>& ylists = g->pred ? g->pred->ylists : root->ylists;   // (as yield_adj)
+    for (const YieldList& y : ylists)
         if (y.mode == mode && y.type == type) return &y;
-    if (root->ylists.size() >= kMaxYieldLists) return nullptr;   // the streamed flags instead
+    if (ylists.size() >= kMaxYieldLists) return nullptr;   // the streamed flags instead
     if (mode != kSym) ensure_inc_yield(g);
     hipStream_t st = g->stream;
     const int64_t A = g->A;
@@ -5890,8 +5894,8 @@ const YieldList* yield_list(hgx_graph* g, int mode, int32_t type) {
     hgx_yl_fill<<<grid, 256, 0, st>>>(A, g->inc_off, g->inc_row, g->inc_type, yf, mode, type, y.off, y.row);
     HGX_CHECK_LAUNCH();
     HGX_HIP(hipStreamSynchronize(st));
-    root->ylists.push_back(y);
-    return &root->ylists.back();
+    ylists.push_back(y);
+    return &ylists.back();
 }
 
 void block_materialize(hgx_graph* g, BlockSet& b) {
@@ -5948,6 +5952,8 @@ struct hgx_seq_result {
     SeqOut lev;                     // the level-synchronous engine's seeds (indexed by rerun order)
     std::vector<int32_t> lev_of;    // [n_seeds] index into lev.segs, or -1
     hgx_graph* g = nullptr;
+    hgx_link_predicate* pred = nullptr;   // the link predicate it was made with: a reference, kept for the lifetime rule
+                                          // only (include/hgx_linkpred.h); no reader of this result uses it
     mutable double ms_total = 0;
     double traversed = 0;
     double ms_block = 0, bytes_block = 0;   // the workgroup engine's launches: device ms, algorithmic bytes
@@ -5997,6 +6003,7 @@ struct hgx_seq_result {
         }
         hbufs.clear();
         lev.bufs.clear();
+        pred_release(pred);
         graph_release(g);
     }
 };
@@ -6231,21 +6238,30 @@ extern "C" {
 
 int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
                      const hgx_algen_opts* opts, hgx_seq_result** out) {
+    return hgx_bfs_sequence_pred(g, seeds, n_seeds, max_depth, opts, nullptr, out);
+}
+
+int hgx_bfs_sequence_pred(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
+                          const hgx_algen_opts* opts, hgx_link_predicate* p, hgx_seq_result** out) {
     HGX_API_BEGIN
-    if (!g || !out || n_seeds < 0 || (n_seeds > 0 && !seeds)) fail(HGX_E_INVALID, "hgx_bfs_sequence: bad argument");
+    const std::string who = p ? "hgx_bfs_sequence_pred" : "hgx_bfs_sequence";
+    if (!g || !out || n_seeds < 0 || (n_seeds > 0 && !seeds)) fail(HGX_E_INVALID, who + ": bad argument");
     *out = nullptr;
-    if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_bfs_sequence: not available on a partition shard");
+    if (g->shard) fail(HGX_E_UNSUPPORTED, who + ": not available on a partition shard");
+    if (p) pred_check(g, p, opts, who.c_str());
     // FIFO order and the discovering link follow the incidence order, i.e. rank order; after an
     // update appended ranks whose handles may sort before existing ones that is not handle order
     // (ADVICE r01), and no re-sort of the output can repair it.
     if (!g->ranks_ordered)
-        fail(HGX_E_UNSUPPORTED, "hgx_bfs_sequence: ranks were appended by hgx_graph_update and may not follow "
+        fail(HGX_E_UNSUPPORTED, who + ": ranks were appended by hgx_graph_update and may not follow "
                                 "handle order (re-assert with HGX_OPT_RANKS_ORDERED or rebuild the snapshot)");
-    const hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
+    hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
+    if (p) o.link_type = kLinkPredKey;   // the typed generator over the predicate's flags
     for (int32_t i = 0; i < n_seeds; ++i)
-        if (seeds[i] < 0 || seeds[i] >= g->A) fail(HGX_E_INVALID, "hgx_bfs_sequence: seed out of range");
-    if (max_depth < -1) fail(HGX_E_INVALID, "hgx_bfs_sequence: bad max_depth");
+        if (seeds[i] < 0 || seeds[i] >= g->A) fail(HGX_E_INVALID, who + ": seed out of range");
+    if (max_depth < -1) fail(HGX_E_INVALID, who + ": bad max_depth");
     std::lock_guard<std::mutex> lk(g->mu);
+    PredScope pred_scope(g, p);
     SeqTrace trace;
     g_seq_trace = trace.on ? &trace : nullptr;
     struct TraceOff {
@@ -6255,6 +6271,7 @@ int hgx_bfs_sequence(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_
     std::unique_ptr<hgx_seq_result> r(new hgx_seq_result());
     r->g = g;
     g->refs.fetch_add(1);
+    r->pred = pred_ref(p);
     SeqCall call(g, seeds, n_seeds, max_depth < 0 ? INT32_MAX : max_depth, o, r.get());
     call.run();
     *out = r.release();

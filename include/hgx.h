@@ -70,8 +70,9 @@ typedef struct hgx_graph_desc {
 
 /* DefaultALGenerator configuration (C/algorithms/DefaultALGenerator.java:437-502).
  * link_type: HGX_NO_TYPE = linkPredicate null, else AtomTypeCondition(type) on the
- * incident link (C/query/AtomTypeCondition.java:121-135).  A siblingPredicate or any
- * other link predicate is not accelerated (the caller keeps the CPU traversal). */
+ * incident link (C/query/AtomTypeCondition.java:121-135).  Any other link predicate over
+ * the accelerated leaves goes through hgx_linkpred.h (a predicate object next to these
+ * options); a siblingPredicate is not accelerated (the caller keeps the CPU traversal). */
 typedef struct hgx_algen_opts {
     int32_t link_type;
     uint8_t return_preceding;    /* default 1 */
