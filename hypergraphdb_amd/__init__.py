@@ -5,7 +5,8 @@ This package is the host-side mirror of the reference interfaces on that path:
   snapshot.HyperGraphSnapshot   the store snapshot (bipartite CSR on the device)
   algorithms                    DefaultALGenerator / HGBreadthFirstTraversal / bfs_batch; LinkPredicate: any tree of
                                 hg.and_ / or_ / not_ over the accelerated leaves as a generator's link predicate
-                                (include/hgx_linkpred.h)
+                                (include/hgx_linkpred.h); AtomPredicate: a type tree or a per-atom mask as its
+                                sibling predicate (include/hgx_sibling.h)
   query                         hg.and/or/type/incident/orderedLink, GpuAndToQuery, GpuOrToQuery, pattern_batch,
                                 pattern_batch_dnf (include/hgx_dnf.h); hg.not_ on its clauses (include/hgx_not.h);
                                 opt-in type-index scans of clauses without an anchor: pattern_batch_dnf(...,
@@ -17,7 +18,7 @@ This package is the host-side mirror of the reference interfaces on that path:
                                 shortest paths read out of a batched BFS (include/hgx_hops.h)
 """
 from ._lib import HGXError, HGXUnsupported, lib  # noqa: F401
-from .algorithms import (AtomTypeCondition, BfsResult, DefaultALGenerator, HGBreadthFirstTraversal,  # noqa: F401
+from .algorithms import (AtomPredicate, AtomTypeCondition, BfsResult, DefaultALGenerator, HGBreadthFirstTraversal,  # noqa: F401
                          HopPaths, LinkPredicate, SequenceResult, bfs_sequence,
                          HGException, bfs_batch)
 from .classics import GraphClassics, LinkWeights, ShortestPathsResult, hop_paths, shortest_paths  # noqa: F401

@@ -92,6 +92,13 @@ EXPORTED_LINKPRED = (
     "hgx_bfs_batch_pred", "hgx_bfs_sequence_pred", "hgx_shortest_paths_pred",
 )
 
+# Every symbol include/hgx_sibling.h declares (checked by tests/test_sibling_abi.py without a GPU).
+EXPORTED_SIBLING = (
+    "hgx_graph_set_atom_types", "hgx_atom_predicate_create", "hgx_atom_predicate_create_mask",
+    "hgx_atom_predicate_free", "hgx_atom_predicate_info", "hgx_atom_predicate_flags", "hgx_bfs_batch_sib",
+    "hgx_shortest_paths_sib",
+)
+
 # Every symbol include/hgx_dnf.h declares (checked by tests/test_dnf_ref.py without a GPU).
 EXPORTED_DNF = ("hgx_pattern_batch_dnf", "hgx_query_result_union_stats")
 
@@ -317,6 +324,16 @@ def lib():
         "hgx_bfs_batch_pred": ([vp, vp, i32, i32, C.POINTER(AlgenOpts), vp, C.POINTER(vp)], C.c_int),
         "hgx_bfs_sequence_pred": ([vp, vp, i32, i32, C.POINTER(AlgenOpts), vp, C.POINTER(vp)], C.c_int),
         "hgx_shortest_paths_pred": ([vp, vp, vp, i32, C.POINTER(AlgenOpts), vp, vp, C.POINTER(vp)], C.c_int),
+        # include/hgx_sibling.h
+        "hgx_graph_set_atom_types": ([vp, vp], C.c_int),
+        "hgx_atom_predicate_create": ([vp, i64, vp, vp, vp, i64, C.POINTER(vp)], C.c_int),
+        "hgx_atom_predicate_create_mask": ([vp, vp, C.POINTER(vp)], C.c_int),
+        "hgx_atom_predicate_free": ([vp], None),
+        "hgx_atom_predicate_info": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double)], C.c_int),
+        "hgx_atom_predicate_flags": ([vp, i64, i64, vp], C.c_int),
+        "hgx_bfs_batch_sib": ([vp, vp, i32, i32, C.POINTER(AlgenOpts), vp, vp, C.POINTER(vp)], C.c_int),
+        "hgx_shortest_paths_sib": ([vp, vp, vp, i32, C.POINTER(AlgenOpts), vp, vp, vp, C.POINTER(vp)], C.c_int),
     }
     for name, (args, res) in sig.items():
         if LIB_VARIANT and not hasattr(L, name):

@@ -99,6 +99,95 @@ class LinkPredicate:
             pass
 
 
+class AtomPredicate:
+    """A sibling predicate of a DefaultALGenerator, evaluated once per atom on the snapshot's device
+    (hgx_atom_predicate, include/hgx_sibling.h), one bit an atom: any tree of hg.and_ / hg.or_ / hg.not_ over
+    hg.type / hg.typePlus, evaluated against the snapshot's atom types (``snapshot.set_atom_types``); anything else
+    in the tree raises HGXUnsupported.  ``from_mask``: any predicate the caller evaluated per atom.  Reusable
+    across calls and across the snapshot's contexts; a result made with it keeps it alive, so closing it first is
+    fine.  While one lives the snapshot refuses updates."""
+
+    def __init__(self, snapshot, cond):
+        self._h = None
+        lit_off, lit, ops = encode_link_predicate(lower_sibling_predicate(cond))
+        h = C.c_void_p()
+        check(lib().hgx_atom_predicate_create(snapshot.handle, len(lit_off) - 1, ptr(lit_off), ptr(lit), ptr(ops),
+                                              len(ops), C.byref(h)))
+        self._attach(snapshot, h, cond)
+
+    @classmethod
+    def from_mask(cls, snapshot, keep):
+        """``keep``: one truth value per atom, or a callable atom -> bool evaluated once per atom."""
+        if callable(keep):
+            keep = [bool(keep(a)) for a in range(snapshot.A)]
+        k = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8)
+        if k.shape != (snapshot.A,):
+            raise ValueError("keep must have one entry per atom")
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().hgx_atom_predicate_create_mask(snapshot.handle, ptr(k), C.byref(h)))
+        self._attach(snapshot, h, None)
+        return self
+
+    def _attach(self, snapshot, h, cond):
+        self._h = h
+        self.snapshot = snapshot
+        self.cond = cond
+        a, nk, ms, by = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+        check(lib().hgx_atom_predicate_info(h, C.byref(a), C.byref(nk), C.byref(ms), C.byref(by)))
+        self.num_atoms, self.num_kept, self._ms, self._bytes = a.value, nk.value, ms.value, by.value
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("atom predicate closed")
+        return self._h
+
+    def flags(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """uint8 per atom of [first, first + n): 1 = the atom satisfies the predicate."""
+        n = self.num_atoms - first if n is None else n
+        out = np.empty(max(n, 1), np.uint8)
+        check(lib().hgx_atom_predicate_flags(self.handle, int(first), int(n), ptr(out) if n else None))
+        return out[:n]
+
+    def stats(self) -> dict:
+        """Device ms of the evaluation kernel (timing enabled) and its algorithmic bytes."""
+        return {"num_atoms": self.num_atoms, "num_kept": self.num_kept, "ms_eval": self._ms,
+                "bytes_eval": self._bytes}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().hgx_atom_predicate_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lower_sibling_predicate(cond):
+    """A sibling tree -> the terms of its disjunctive normal form (``lower_link_predicate``), every literal a
+    hg.type / hg.typePlus leaf; any other leaf raises HGXUnsupported (on a node atom those leaves have rules of
+    their own in the reference: evaluate them per atom and use ``AtomPredicate.from_mask``)."""
+    from .query import TypePlusCondition
+    terms = lower_link_predicate(cond)
+    for term in terms:
+        for leaf, _ in term:
+            if not isinstance(leaf, (AtomTypeCondition, TypePlusCondition)):
+                raise _lib.HGXUnsupported(_lib.HGX_E_UNSUPPORTED, f"sibling predicate leaf {leaf!r}: only hg.type / "
+                                                                  "hg.typePlus are evaluated on atoms")
+    return terms
+
+
 def lower_link_predicate(cond):
     """A condition tree -> the terms of its disjunctive normal form, tuples of (leaf, polarity) literals: the
     lowering of a negated tree (query.lower_not) applied to the tree itself, without the outer Not."""
@@ -129,7 +218,10 @@ class DefaultALGenerator:
     """Adjacency-list generator configuration.  linkPredicate: None, an AtomTypeCondition (both through the
     type key of hgx_algen_opts), a LinkPredicate, or a raw tree of hg.and_ / hg.or_ / hg.not_ over the
     accelerated leaves, which every call compiles into a LinkPredicate of its own and releases when it returns
-    (include/hgx_linkpred.h).  A siblingPredicate is not accelerated (HGXUnsupported)."""
+    (include/hgx_linkpred.h).  siblingPredicate (include/hgx_sibling.h; bfs_batch, hop_paths, shortest_paths and
+    GraphClassics.dijkstra only -- ``options()`` / ``compiled()`` and so every other caller keep refusing it): None,
+    an AtomPredicate, a raw tree over hg.type / hg.typePlus compiled per call against the snapshot's atom types,
+    or a callable atom -> bool evaluated once per atom into a mask."""
 
     def __init__(self, graph, link_predicate=None, sibling_predicate=None, return_preceding=True,
                  return_succeeding=True, reverse_order=False, return_source=None):
@@ -173,6 +265,28 @@ class DefaultALGenerator:
         if isinstance(lp, LinkPredicate):
             return opts, lp, False
         return opts, LinkPredicate(snapshot, lp), True
+
+    def compiled_sibling(self, snapshot):
+        """(options, LinkPredicate or None, AtomPredicate or None, owned): ``compiled`` for the entry points
+        that take a sibling predicate (hgx_bfs_batch_sib, hgx_shortest_paths_sib).  owned: the predicates made
+        for this call, which the caller closes when its call returns."""
+        sp = self.sibling_predicate
+        if sp is None:
+            opts, lp, owned = self.compiled(snapshot)
+            return opts, lp, None, ([lp] if owned else [])
+        bare = DefaultALGenerator(self.graph, self.link_predicate, None, self.return_preceding,
+                                  self.return_succeeding, self.reverse_order, self.return_source)
+        opts, lp, owned = bare.compiled(snapshot)
+        made = [lp] if owned else []
+        try:
+            if isinstance(sp, AtomPredicate):
+                return opts, lp, sp, made
+            ap = AtomPredicate.from_mask(snapshot, sp) if callable(sp) else AtomPredicate(snapshot, sp)
+        except BaseException:
+            for p in made:
+                p.close()
+            raise
+        return opts, lp, ap, made + [ap]
 
 
 class BfsResult:
@@ -337,18 +451,21 @@ class HopPaths:
 def bfs_batch(snapshot, seeds, max_depth=None, generator: DefaultALGenerator | None = None) -> BfsResult:
     """HGBreadthFirstTraversal(seeds[i], generator, max_depth) for every i, run together on the GPU."""
     gen = generator or DefaultALGenerator(snapshot)
-    opts, pred, owned = gen.compiled(snapshot)
+    opts, pred, apred, owned = gen.compiled_sibling(snapshot)
     s = np.ascontiguousarray(seeds, np.int32)
     md = _lib.HGX_UNBOUNDED if max_depth is None or max_depth >= 2**31 - 1 else int(max_depth)
     h = C.c_void_p()
     try:
-        if pred is None:
+        if apred is not None:
+            check(lib().hgx_bfs_batch_sib(snapshot.handle, ptr(s), len(s), md, C.byref(opts),
+                                          None if pred is None else pred.handle, apred.handle, C.byref(h)))
+        elif pred is None:
             check(lib().hgx_bfs_batch(snapshot.handle, ptr(s), len(s), md, C.byref(opts), C.byref(h)))
         else:
             check(lib().hgx_bfs_batch_pred(snapshot.handle, ptr(s), len(s), md, C.byref(opts), pred.handle, C.byref(h)))
     finally:
-        if owned:
-            pred.close()   # the result holds its own reference
+        for p in owned:
+            p.close()   # the result holds its own references
     return BfsResult(snapshot, h, s)
 
 

@@ -160,11 +160,14 @@ def shortest_paths(snapshot, starts, goals, generator: DefaultALGenerator | None
     else:
         own = LinkWeights.from_mapping(snapshot, weights) if callable(weights) else LinkWeights(snapshot, weights)
         wh = own.handle
-    pred, owned = None, False
+    owned = []
     try:
-        opts, pred, owned = gen.compiled(snapshot)
+        opts, pred, apred, owned = gen.compiled_sibling(snapshot)
         h = C.c_void_p()
-        if pred is None:
+        if apred is not None:
+            check(lib().hgx_shortest_paths_sib(snapshot.handle, ptr(s), ptr(g), len(s), C.byref(opts), wh,
+                                               None if pred is None else pred.handle, apred.handle, C.byref(h)))
+        elif pred is None:
             check(lib().hgx_shortest_paths(snapshot.handle, ptr(s), ptr(g), len(s), C.byref(opts), wh, C.byref(h)))
         else:
             check(lib().hgx_shortest_paths_pred(snapshot.handle, ptr(s), ptr(g), len(s), C.byref(opts), wh,
@@ -172,8 +175,8 @@ def shortest_paths(snapshot, starts, goals, generator: DefaultALGenerator | None
     finally:
         if own is not None:
             own.close()
-        if owned:
-            pred.close()   # the result holds its own reference
+        for p in owned:
+            p.close()   # the result holds its own references
     return ShortestPathsResult(snapshot, h, s, g)
 
 

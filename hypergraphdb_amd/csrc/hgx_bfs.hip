@@ -4990,6 +4990,13 @@ struct LevelLoop {
         const int n = (int)seed_atoms.size();
         hgx_seed<W><<<grid_for(n, 256, 1 << 20), 256, 0, s>>>(n, d_atoms, d_rows, bt.lvl[0], vis, bt.fa[0], ever, full, fm);
         HGX_CHECK_LAUNCH();
+        // Sibling predicate (include/hgx_sibling.h): every atom that fails it is visited by every
+        // traversal before level 1, so no level kind can produce it as new.  A failing seed keeps its lvl[0] row and
+        // its fa[0] bit: it is expanded once, as in the reference.
+        if (g->sib) {
+            sib_saturate(g->sib, A, W, fm.w, vis, ever, full, s);
+            full_total = (u64)g->sib_fail;
+        }
         // Readout counting next to the traversal (A/B, HGX_COUNT_EAGER=1): a level's rows are final once
         // it is produced, so its counting pass can run on a second stream while the following levels run.
         // Measured slower on config 2 (19.36 against 18.66 ms for traversal + readout,
@@ -5868,26 +5875,35 @@ void ensure_accounting(hgx_bfs_result* r) {
 }
 
 void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
-                    const hgx_algen_opts* opts, hgx_bfs_result** out, hgx_link_predicate* pred = nullptr);
+                    const hgx_algen_opts* opts, hgx_bfs_result** out, hgx_link_predicate* pred = nullptr,
+                    hgx_atom_predicate* ap = nullptr);
 
-// hgx_bfs_batch and hgx_bfs_batch_pred (pred null: the former)
+// hgx_bfs_batch, hgx_bfs_batch_pred (pred null: the former) and hgx_bfs_batch_sib (ap null: the one before)
 void bfs_batch_entry(const char* who, hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
-                     const hgx_algen_opts* opts, hgx_link_predicate* pred, hgx_bfs_result** out) {
+                     const hgx_algen_opts* opts, hgx_link_predicate* pred, hgx_bfs_result** out,
+                     hgx_atom_predicate* ap = nullptr) {
     const std::string w(who);
     if (!g || !out || n_seeds < 0 || (n_seeds > 0 && !seeds)) fail(HGX_E_INVALID, w + ": bad argument");
     *out = nullptr;
     if (g->shard) {
-        if (pred) fail(HGX_E_UNSUPPORTED, w + ": not available on a partition shard");
+        if (pred || ap) fail(HGX_E_UNSUPPORTED, w + ": not available on a partition shard");
         fail(HGX_E_INVALID, w + ": a partition shard needs hgx_pbfs_batch (a transport)");
     }
     if (pred) pred_check(g, pred, opts, who);
+    if (ap) apred_check(g, ap, who);
     for (int32_t i = 0; i < n_seeds; ++i)
         if (seeds[i] < 0 || seeds[i] >= g->A) fail(HGX_E_INVALID, w + ": seed out of range");
     if (max_depth < -1) fail(HGX_E_INVALID, w + ": bad max_depth");
-    bfs_batch_impl(g, nullptr, seeds, n_seeds, max_depth, opts, out, pred);
+    bfs_batch_impl(g, nullptr, seeds, n_seeds, max_depth, opts, out, pred, ap);
 }
 
 }  // namespace
+
+void hgx::bfs_batch_sib(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth, const hgx_algen_opts* opts,
+                        hgx_link_predicate* p, hgx_atom_predicate* ap, hgx_bfs_result** out) {
+    bfs_batch_entry(ap ? "hgx_bfs_batch_sib" : p ? "hgx_bfs_batch_pred" : "hgx_bfs_batch", g, seeds, n_seeds, max_depth,
+                    opts, p, out, ap);
+}
 
 extern "C" {
 
@@ -6050,12 +6066,13 @@ void account_level(hgx_bfs_result* r, const BfsBatch& bt, int mode, int d, const
 }
 
 void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n_seeds, int32_t max_depth,
-                    const hgx_algen_opts* opts, hgx_bfs_result** out, hgx_link_predicate* pred) {
+                    const hgx_algen_opts* opts, hgx_bfs_result** out, hgx_link_predicate* pred, hgx_atom_predicate* ap) {
     hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
     if (pred) o.link_type = kLinkPredKey;   // the typed generator over the predicate's flags
     const ShardInfo* shp = g->shard;
     std::lock_guard<std::mutex> lk(g->mu);
     PredScope pred_scope(g, pred);
+    SibScope sib_scope(g, ap);
     HGX_HIP(hipSetDevice(g->device));
     const int mode = mode_of(o);
 
@@ -6075,12 +6092,14 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
             if (r->blk) block_release(r->g, *r->blk);
             r->g->refs.fetch_sub(1);   // the caller still holds its own reference
             pred_release(r->pred);     // (likewise)
+            apred_release(r->apred);
             delete r;
         }
     } guard{r};
     r->g = g;
     g->refs.fetch_add(1);
     r->pred = pred_ref(pred);
+    r->apred = apred_ref(ap);
     r->n_seeds = n_seeds;
     r->typed = o.link_type >= 0;
     r->opts = o;
@@ -6090,9 +6109,10 @@ void bfs_batch_impl(hgx_graph* g, Transport* tr, const int32_t* seeds, int32_t n
     std::vector<LevelRec> level_ctr;
     int max_expanded = 0;
     // Whole-graph batches: every seed first runs in one workgroup (hgx_bfs_block); the rows engine
-    // below takes the seeds that outgrew it, compacted.
+    // below takes the seeds that outgrew it, compacted.  Not with a sibling predicate: the workgroup engine does not
+    // read its bits, every seed runs on the rows engine.
     std::vector<int32_t> rseeds;
-    if (!shp && !tr && g->bfs_block && n_seeds > 0) {
+    if (!shp && !tr && g->bfs_block && !ap && n_seeds > 0) {
         r->blk.reset(new BlockSet());
         bfs_block(g, seeds, n_seeds, max_depth, o, *r->blk);
         const BlockSet& b = *r->blk;
@@ -6370,8 +6390,10 @@ void hgx_bfs_result_free(hgx_bfs_result* r) {
         if (r->hop_key) g->release(r->hop_key, sizeof(u64) * (size_t)std::max<int64_t>(g->A, 1));
     }
     hgx_link_predicate* const pred = r->pred;
+    hgx_atom_predicate* const apred = r->apred;
     delete r;
     pred_release(pred);
+    apred_release(apred);
     if (g) graph_release(g);
 }
 

@@ -44,6 +44,7 @@ void graph_release(hgx_graph* g) {
     if (!b) {
         if (g->link_type) (void)hipFree(g->link_type);
         if (g->inc_type) (void)hipFree(g->inc_type);
+        if (g->atom_type) (void)hipFree(g->atom_type);   // (hgx_graph_set_atom_types: a snapshot's only)
     }
     HGX_FREE_OWN(inc_ts_type); HGX_FREE_OWN(inc_ts_tgt); HGX_FREE_OWN(heavy_atom); HGX_FREE_OWN(chunks);
     HGX_FREE_OWN(hasinc); HGX_FREE_OWN(nbr_hint); HGX_FREE_OWN(top_list); HGX_FREE_OWN(inc_yf); HGX_FREE_OWN(pchunks); HGX_FREE_OWN(type_idx);

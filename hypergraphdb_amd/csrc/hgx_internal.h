@@ -32,6 +32,7 @@
 #include "../../include/hgx_not.h"
 #include "../../include/hgx_paths.h"
 #include "../../include/hgx_scan.h"
+#include "../../include/hgx_sibling.h"
 
 namespace hgx {
 
@@ -319,6 +320,9 @@ struct hgx_graph {
     int32_t sc_ok = -1;                             // order-exact grid stage (hgx_seq_coop): its grid (0: does not fit)
     int64_t sc_pcap = 0;                            //   its pair capacity (grown on demand)
     hgx_link_predicate* pred = nullptr;             // the link predicate of the traversal in progress (PredScope; under mu)
+    const unsigned long long* sib = nullptr;        // the sibling predicate's bits of the traversal in progress (SibScope;
+                                                    //   under mu): bit a set = atom a may be yielded; null = no predicate
+    int64_t sib_fail = 0;                           //   and the atoms whose bit is 0
     std::deque<hgx::YieldList> ylists;              // yield lists (snapshot only; contexts read their base's)
     std::deque<hgx::YieldAdj> yadjs;                // yield adjacencies (likewise)
     std::mutex ylist_mu;
@@ -352,6 +356,10 @@ struct hgx_graph {
     int64_t* inc_off = nullptr;
     int32_t* inc_row = nullptr;
     int32_t* inc_type = nullptr;    // [I] link_type[inc_row[i]]: streamed type filter of the query path
+    // The optional type key of every atom (hgx_graph_set_atom_types, include/hgx_sibling.h): snapshot only, read
+    // and replaced under the snapshot's mutex; type_preds = the living atom predicates evaluated from it.
+    int32_t* atom_type = nullptr;   // [A]
+    std::atomic<int> type_preds{0};
     // Type-grouped incidence (built on the first pattern query): inside each atom's segment the link
     // rows ordered by (type, row), so the links of one type incident to an atom are one contiguous,
     // ascending range (found by binary search over inc_ts_type).
@@ -418,6 +426,17 @@ struct hgx_link_predicate {
     std::deque<hgx::YieldAdj> yadjs;
 };
 
+// A sibling predicate (include/hgx_sibling.h, hgx_sibling.hip): one bit an atom, 64 atoms to a word, the bits
+// past the last atom zero.
+struct hgx_atom_predicate {
+    hgx_graph* root = nullptr;       // the snapshot (a reference is held)
+    std::atomic<int> refs{1};        // the caller's handle + one per result made with it
+    int64_t A = 0, n_kept = 0;
+    unsigned long long* bits = nullptr;   // [A / 64 + 2]
+    bool typed = false;              // evaluated from the snapshot's atom-type column (counted in root->type_preds)
+    double ms_eval = 0, bytes_eval = 0;
+};
+
 namespace hgx {
 // A reference for a result (p may be null) / dropping one: the last frees the arrays, the lists and the
 // predicate's reference on its snapshot.  Neither needs a graph mutex.
@@ -450,6 +469,41 @@ struct PredScope {
     PredScope(const PredScope&) = delete;
     PredScope& operator=(const PredScope&) = delete;
 };
+// The same for a sibling predicate; apred_check: ap (not null) belongs to g's snapshot.
+inline hgx_atom_predicate* apred_ref(hgx_atom_predicate* p) {
+    if (p) p->refs.fetch_add(1);
+    return p;
+}
+void apred_release(hgx_atom_predicate* p);
+void apred_check(const hgx_graph* g, const hgx_atom_predicate* ap, const char* who);
+// While alive, g's traversal code sees ap's bits in g->sib (ap null: nothing changes).  The caller holds g->mu.
+struct SibScope {
+    hgx_graph* g;
+    SibScope(hgx_graph* gg, const hgx_atom_predicate* ap) : g(gg) {
+        g->sib = ap ? ap->bits : nullptr;
+        g->sib_fail = ap ? ap->A - ap->n_kept : 0;
+    }
+    ~SibScope() {
+        g->sib = nullptr;
+        g->sib_fail = 0;
+    }
+    SibScope(const SibScope&) = delete;
+    SibScope& operator=(const SibScope&) = delete;
+};
+// The host checks of hgx_graph_set_atom_types over host copies of the link rows' atoms and types.
+void atom_types_validate(int64_t A, int64_t M, const int32_t* atom_type, const int32_t* link_atom,
+                         const int32_t* link_type);
+// The batched BFS's sibling prologue (hgx_sibling.hip), enqueued on s after the seeds are written:
+// every atom whose bit of keep is 0 gets vis row = fm (W words) and its ever / full bits.
+void sib_saturate(const unsigned long long* keep, int64_t A, int W, const unsigned long long* fm,
+                  unsigned long long* vis, unsigned long long* ever, unsigned long long* full, hipStream_t s);
+// hgx_bfs_batch_sib / hgx_shortest_paths_sib behind the ABI's try block (hgx_bfs.hip, hgx_paths.hip); ap null:
+// the _pred entry point.
+void bfs_batch_sib(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t max_depth, const hgx_algen_opts* opts,
+                   hgx_link_predicate* p, hgx_atom_predicate* ap, hgx_bfs_result** out);
+void shortest_paths_sib(hgx_graph* g, const int32_t* starts, const int32_t* goals, int32_t n_pairs,
+                        const hgx_algen_opts* opts, const hgx_link_weights* w, hgx_link_predicate* p,
+                        hgx_atom_predicate* ap, hgx_sp_result** out);
 void graph_release(hgx_graph* g);
 void free_yield_lists(hgx_graph* g);   // (hgx_graph_update: the incidence changed)   // drop a reference; frees at zero
 // Builds the BFS's first-use read-only tables (has-incidence bitmap, yield flags, push chunks) on g
@@ -656,6 +710,9 @@ int not_check_literal(int64_t A, const NotProgram& p, int64_t l, std::string& wh
 // terms; fills p.n_terms / p.n_lits and tells whether a literal reads targets.  Messages name the term and the
 // literal.
 void linkpred_validate(int64_t A, int64_t n_terms, NotProgram& p, bool* needs_targets);
+// The host checks of hgx_atom_predicate_create's program (hgx_sibling.hip): those of linkpred_validate, and
+// HGX_E_UNSUPPORTED for a literal that is no HGX_NOT_TYPE.  Fills p.n_terms / p.n_lits.
+void atompred_validate(int64_t A, int64_t n_terms, NotProgram& p);
 // Its device copy (neg_off == nullptr: the batch has no negation).
 struct NotDev {
     const int64_t* neg_off = nullptr;
@@ -779,6 +836,8 @@ struct hgx_bfs_result {
     bool typed = false;
     hgx_algen_opts opts{HGX_NO_TYPE, 1, 1, 0, 0};   // the generator the result was made with (hgx_hops.h readers)
     hgx_link_predicate* pred = nullptr;             // its link predicate (a reference; opts.link_type is then kLinkPredKey)
+    hgx_atom_predicate* apred = nullptr;            // its sibling predicate (a reference, kept for the lifetime rule only:
+                                                    //   the level rows already leave out the atoms that fail it)
     std::map<int32_t, int32_t> isolated;   // shards: seed index -> owned seed atom without incidence
     std::vector<int64_t> counts;   // [n_seeds * n_levels]
     // Seeds finished by the workgroup engine (HGX_OPT_BFS_BLOCK); the batches then hold only the

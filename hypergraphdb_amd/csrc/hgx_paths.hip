@@ -64,6 +64,7 @@ struct SpArgs {
     uint32_t* stamp;           // [K * A] round an atom was last queued in; after convergence: plateau levels
     u64* pd;                   // [K * A] least distance of a tight predecessor
     u64* pk;                   // [K * A] (predecessor atom << 32) | link atom
+    const u64* keep;           // sibling predicate: bit t set = atom t may be yielded; nullptr = no test
     const u64* items;          // this launch's work items
     int64_t n_items;
     u64* next;                 // the list this launch appends to, its counter and capacity
@@ -212,7 +213,8 @@ __global__ void __launch_bounds__(256) hgx_sp_walk(SpArgs a) {
                 if (act) {
                     t = a.tgt_idx[p];
                     ++p;
-                    act = t != v;
+                    // (siblingPredicate: a target that fails is not yielded, DefaultALGenerator.java:120-150)
+                    act = t != v && (!a.keep || ((a.keep[t >> 6] >> (t & 63)) & 1ull));
                 }
                 if (OP == kRelax) {
                     bool imp = false, app = false;
@@ -366,6 +368,7 @@ struct hgx_sp_result {
     hgx_graph* g = nullptr;
     hgx_link_predicate* pred = nullptr;   // the link predicate it was made with: a reference, kept for the lifetime rule
                                           // only (include/hgx_linkpred.h); no reader of this result uses it
+    hgx_atom_predicate* apred = nullptr;  // its sibling predicate, likewise (include/hgx_sibling.h)
     int32_t n_pairs = 0;
     int64_t A = 0;
     std::vector<int32_t> goals;
@@ -456,6 +459,7 @@ void sp_run(hgx_graph* g, const int32_t* starts, const int32_t* goals, int32_t n
     a.tgt_off = g->tgt_off;
     a.tgt_idx = g->tgt_idx;
     a.link_atom = g->link_atom;
+    a.keep = g->sib;
     a.w = lw ? lw->w : nullptr;
     a.dist = dist;
     a.stamp = stamp;
@@ -668,15 +672,27 @@ int hgx_shortest_paths_pred(hgx_graph* g, const int32_t* starts, const int32_t* 
                             const hgx_algen_opts* opts, const hgx_link_weights* w, hgx_link_predicate* p,
                             hgx_sp_result** out) {
     HGX_API_BEGIN
-    const std::string who = p ? "hgx_shortest_paths_pred" : "hgx_shortest_paths";
+    shortest_paths_sib(g, starts, goals, n_pairs, opts, w, p, nullptr, out);
+    HGX_API_END
+}
+
+}  // extern "C"
+
+// hgx_shortest_paths, hgx_shortest_paths_pred (p null: the former) and hgx_shortest_paths_sib (ap null: the one before)
+void hgx::shortest_paths_sib(hgx_graph* g, const int32_t* starts, const int32_t* goals, int32_t n_pairs,
+                             const hgx_algen_opts* opts, const hgx_link_weights* w, hgx_link_predicate* p,
+                             hgx_atom_predicate* ap, hgx_sp_result** out) {
+    const std::string who = ap ? "hgx_shortest_paths_sib" : p ? "hgx_shortest_paths_pred" : "hgx_shortest_paths";
     if (!g || !out || n_pairs < 0 || (n_pairs > 0 && (!starts || !goals))) fail(HGX_E_INVALID, who + ": bad argument");
     *out = nullptr;
     if (g->shard) fail(HGX_E_UNSUPPORTED, who + ": not available on a partition shard");
     if (p) pred_check(g, p, opts, who.c_str());
+    if (ap) apred_check(g, ap, who.c_str());
     hgx_algen_opts o = opts ? *opts : hgx_algen_opts{HGX_NO_TYPE, 1, 1, 0, 0};
     if (p) o.link_type = kLinkPredKey;   // the typed generator over the predicate's flags
     std::lock_guard<std::mutex> lk(g->mu);
     PredScope pred_scope(g, p);
+    SibScope sib_scope(g, ap);
     for (int32_t i = 0; i < n_pairs; ++i) {
         if (starts[i] < 0 || starts[i] >= g->A) fail(HGX_E_INVALID, who + ": start out of range");
         if (goals[i] != HGX_NO_GOAL && (goals[i] < 0 || goals[i] >= g->A)) fail(HGX_E_INVALID, who + ": goal out of range");
@@ -693,12 +709,14 @@ int hgx_shortest_paths_pred(hgx_graph* g, const int32_t* starts, const int32_t* 
             release_rows(r);
             r->g->refs.fetch_sub(1);   // the caller still holds its own reference
             pred_release(r->pred);     // (likewise)
+            apred_release(r->apred);
             delete r;
         }
     } guard{r};
     r->g = g;
     g->refs.fetch_add(1);
     r->pred = pred_ref(p);
+    r->apred = apred_ref(ap);
     r->n_pairs = n_pairs;
     r->A = g->A;
     r->goals.assign(goals, goals + n_pairs);
@@ -709,8 +727,9 @@ int hgx_shortest_paths_pred(hgx_graph* g, const int32_t* starts, const int32_t* 
     if (n_pairs > 0) sp_run(g, starts, goals, n_pairs, o, w, r);
     guard.r = nullptr;
     *out = r;
-    HGX_API_END
 }
+
+extern "C" {
 
 int hgx_sp_result_info(const hgx_sp_result* r, int32_t* n_pairs) {
     HGX_API_BEGIN
@@ -800,8 +819,10 @@ void hgx_sp_result_free(hgx_sp_result* r) {
         release_rows(r);
     }
     hgx_link_predicate* const pred = r->pred;
+    hgx_atom_predicate* const apred = r->apred;
     delete r;
     pred_release(pred);
+    apred_release(apred);
     if (g) graph_release(g);
 }
 

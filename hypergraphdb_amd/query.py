@@ -234,9 +234,10 @@ class TargetAt:
 
 class BFSCondition:
     def __init__(self, start, link_predicate=None, return_preceding=True, return_succeeding=True,
-                 reverse_order=False, max_distance=None):
+                 reverse_order=False, max_distance=None, sibling_predicate=None):
         self.start = int(start)
         self.link_predicate = link_predicate
+        self.sibling_predicate = sibling_predicate   # not accelerated here: find_all raises HGXUnsupported
         self.flags = (return_preceding, return_succeeding, reverse_order)
         self.max_distance = max_distance
 
@@ -293,8 +294,10 @@ class hg:
         return Not(pred)
 
     @staticmethod
-    def bfs(start, link_predicate=None, return_preceding=True, return_succeeding=True, reverse_order=False):
-        return BFSCondition(start, link_predicate, return_preceding, return_succeeding, reverse_order)
+    def bfs(start, link_predicate=None, return_preceding=True, return_succeeding=True, reverse_order=False,
+            sibling_predicate=None):
+        return BFSCondition(start, link_predicate, return_preceding, return_succeeding, reverse_order,
+                            sibling_predicate=sibling_predicate)
 
     @staticmethod
     def subsumed(general, subsumes_type):
@@ -1113,7 +1116,7 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
     if isinstance(cond, BFSCondition):
         # TraversalBasedQuery(traversal, ReturnType.targets) (ToQueryMap.java:313-319): the atoms
         # in HGBreadthFirstTraversal.next() order
-        gen = DefaultALGenerator(snapshot, cond.link_predicate, None, *cond.flags)
+        gen = DefaultALGenerator(snapshot, cond.link_predicate, cond.sibling_predicate, *cond.flags)
         seq = bfs_sequence(snapshot, [cond.start], cond.max_distance, gen)
         return seq.pairs(0)[1].tolist()
     if isinstance(cond, MapCondition):

@@ -270,6 +270,19 @@ class HyperGraphSnapshot:
         check(lib().hgx_graph_type_links(self.handle, ptr(t), len(t), ptr(out)))
         return out
 
+    def set_atom_types(self, atom_type):
+        """The type key of every atom, link atoms and node atoms alike (hgx_graph_set_atom_types,
+        include/hgx_sibling.h): what a type tree used as a sibling predicate is evaluated against.  One value
+        per atom, a link atom's equal to its link type; None drops the column.  ``update`` drops it too: set it
+        again afterwards.  Not on a context."""
+        if atom_type is None:
+            check(lib().hgx_graph_set_atom_types(self.handle, None))
+            return
+        t = np.ascontiguousarray(atom_type, np.int32)
+        if t.shape != (self.A,):
+            raise ValueError("atom_type must have one entry per atom")
+        check(lib().hgx_graph_set_atom_types(self.handle, ptr(t)))
+
     def context(self):
         """An execution context of this snapshot (hgx_graph_context): shares the device arrays, has its
         own stream, lock and scratch, so traversals on it run next to the ones on this snapshot (e.g.

@@ -72,7 +72,7 @@ typedef struct hgx_graph_desc {
  * link_type: HGX_NO_TYPE = linkPredicate null, else AtomTypeCondition(type) on the
  * incident link (C/query/AtomTypeCondition.java:121-135).  Any other link predicate over
  * the accelerated leaves goes through hgx_linkpred.h (a predicate object next to these
- * options); a siblingPredicate is not accelerated (the caller keeps the CPU traversal). */
+ * options); a siblingPredicate goes through hgx_sibling.h (an atom predicate object next to them). */
 typedef struct hgx_algen_opts {
     int32_t link_type;
     uint8_t return_preceding;    /* default 1 */

@@ -18,8 +18,8 @@
  *   hgx_bfs_batch_pred, hgx_bfs_sequence_pred, hgx_shortest_paths_pred
  *                              <- the traversals of hgx.h / hgx_paths.h with such a generator.
  *
- * Not accelerated: a siblingPredicate (it needs the types of node atoms, which the snapshot does not hold), and
- * partition shards (hgx_pbfs_batch keeps the single link type).
+ * A siblingPredicate goes through hgx_sibling.h (the types of node atoms are an optional column there).  Not
+ * accelerated: partition shards (hgx_pbfs_batch keeps the single link type).
  */
 #ifndef HGX_LINKPRED_H
 #define HGX_LINKPRED_H
