@@ -12,7 +12,10 @@ This package is the host-side mirror of the reference interfaces on that path:
                                 opt-in type-index scans of clauses without an anchor: pattern_batch_dnf(...,
                                 type_scan=True), GpuScanToQuery (include/hgx_scan.h); hg.apply(hg.targetAt) and
                                 the And of such projections on the device: pattern_batch_join, join_parts,
-                                GpuMapToQuery (include/hgx_join.h)
+                                GpuMapToQuery (include/hgx_join.h); over every atom, with the atom types set
+                                (snapshot.set_atom_types): pattern_batch_atoms, atom_parts -- type scans that
+                                deliver node atoms too and a type tree or mask on the projected atoms
+                                (include/hgx_atoms.h)
   classics                      GraphClassics.dijkstra / shortest_paths (include/hgx_paths.h);
                                 hop_paths -> HopPaths, BfsResult.paths / depths / predecessors: unit-weight
                                 shortest paths read out of a batched BFS (include/hgx_hops.h)
@@ -24,7 +27,8 @@ from .algorithms import (AtomPredicate, AtomTypeCondition, BfsResult, DefaultALG
 from .classics import GraphClassics, LinkWeights, ShortestPathsResult, hop_paths, shortest_paths  # noqa: F401
 from .query import (And, ArityCondition, GpuAndToQuery, GpuMapToQuery, GpuOrToQuery, GpuScanToQuery,  # noqa: F401
                     HGQueryConfiguration, LinkCondition, MapCondition, Not, Or, PositionedIncidentCondition, TargetAt,
-                    TypePlusCondition, find_all, hg, join_parts, pattern_batch, pattern_batch_dnf, pattern_batch_join,
+                    TypePlusCondition, atom_parts, find_all, hg, join_parts, pattern_batch, pattern_batch_atoms, pattern_batch_dnf,
+                    pattern_batch_join,
                     to_dnf)
 from .snapshot import HyperGraphSnapshot, export_store, rank_handles, read_snapshot, write_snapshot  # noqa: F401
 

@@ -113,6 +113,10 @@ EXPORTED_JOIN = ("hgx_pattern_batch_join", "hgx_query_result_join_stats")
 HGX_JOIN_SELF = -1
 HGX_JOIN_TYPE_SCAN = 1
 
+# Every symbol include/hgx_atoms.h declares (checked by tests/test_atoms_abi.py without a GPU).
+EXPORTED_ATOMS = ("hgx_graph_type_atoms", "hgx_pattern_batch_atoms", "hgx_query_result_atoms_stats")
+HGX_ATOMS_TYPE_SCAN = 1
+
 # Every symbol include/hgx_hops.h declares (checked by tests/test_hop_ref.py without a GPU).
 EXPORTED_HOPS = (
     "hgx_bfs_result_paths", "hgx_hop_paths_info", "hgx_hop_paths_offsets", "hgx_hop_paths_read", "hgx_hop_paths_stats",
@@ -305,6 +309,12 @@ def lib():
                                     i32, C.POINTER(vp)], C.c_int),
         "hgx_query_result_join_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64),
                                          C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+        # include/hgx_atoms.h
+        "hgx_graph_type_atoms": ([vp, vp, i64, vp], C.c_int),
+        "hgx_pattern_batch_atoms": ([vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                     i64, i32, C.POINTER(vp)], C.c_int),
+        "hgx_query_result_atoms_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)], C.c_int),
         # include/hgx_hops.h
         "hgx_bfs_result_paths": ([vp, vp, vp, i32, C.POINTER(vp)], C.c_int),
         "hgx_hop_paths_info": ([vp, C.POINTER(i32), C.POINTER(i64)], C.c_int),

@@ -467,6 +467,7 @@ int hgx_graph_update(hgx_graph* g, int64_t num_atoms, int64_t n_add, const int32
     drop_type_index(g);
     if (g->atom_type) (void)hipFree(g->atom_type);   // the id space may have grown: the caller sets the types again
     g->atom_type = nullptr;                          //   (include/hgx_sibling.h)
+    g->atom_index.reset();                           //   and the atom index goes with them (include/hgx_atoms.h)
     if (g->co_vis) (void)hipFree(g->co_vis);   // per-seed bitmaps sized by the old atom count
     g->co_vis = nullptr;
     g->co_vis_seeds = 0;

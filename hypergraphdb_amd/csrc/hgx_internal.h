@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/hgx_atoms.h"
 #include "../../include/hgx_dnf.h"
 #include "../../include/hgx_hops.h"
 #include "../../include/hgx_join.h"
@@ -254,6 +255,23 @@ struct QueryCombiner {
 
 }  // namespace hgx
 
+namespace hgx {
+// The atom index (include/hgx_atoms.h, hgx_atoms.hip): one 16-byte record per atom in the layout of the link
+// index -- (atom, arity, first target offset low / high word); a node: arity 0 and the high word kAtomNode -- the
+// atoms stably sorted by atom_type, so a type is one segment whose atoms ascend.  key / seg: the sorted distinct
+// type keys and their segment offsets, on the host.  Shared: a context holds a reference on its snapshot's index,
+// so a replaced atom-type column never frees an index a context's batch still reads.
+constexpr int32_t kAtomNode = -1;
+struct AtomIndex {
+    int4* idx = nullptr;          // [A]
+    std::vector<int32_t> key;     // [n distinct types] ascending
+    std::vector<int64_t> seg;     // [n distinct types + 1]
+    ~AtomIndex() {
+        if (idx) (void)hipFree(idx);
+    }
+};
+}  // namespace hgx
+
 struct hgx_comm {
     hgx::Transport* t = nullptr;
 };
@@ -379,6 +397,9 @@ struct hgx_graph {
     bool type_idx_built = false;
     std::vector<int32_t> type_key;   // [n distinct types] ascending
     std::vector<int64_t> type_seg;   // [n distinct types + 1]
+    // The atom index over atom_type (hgx_atoms.hip, built on the first use): the snapshot's is dropped with the
+    // column; a context copies its snapshot's reference at every batch that scans.
+    std::shared_ptr<hgx::AtomIndex> atom_index;
 
     int64_t n_heavy = 0;            // heavy atoms (deg > kHeavyDegree)
     int64_t I_heavy = 0;            // incidence entries of heavy atoms
@@ -677,6 +698,9 @@ struct JoinArgs {
     unsigned long long* out_ctr; // [8] mapped: ctr, [2] = ids kept
     int64_t* out_off;            // [n_queries + 1] mapped: result offsets
     int32_t* out_ids;            // [cap] mapped: result ids (atoms)
+    // hgx_pattern_batch_atoms: the bits of each join query's atom predicate (a null entry: none), or null: a batch
+    // without predicates, which runs the keep kernel without the filter.  ctr[6] / [7]: values tested / rejected.
+    const unsigned long long* const* keep_bits;   // [n_queries]
 };
 // Bits of the part field of a key: enough for the pad key's part, n_parts.
 inline int32_t join_part_bits(int64_t n_parts) {
@@ -685,10 +709,19 @@ inline int32_t join_part_bits(int64_t n_parts) {
     return b;
 }
 size_t join_temp_bytes(int64_t cap, int32_t sort_bits, hipStream_t s);
-// Enqueues the join on s: no synchronisation, nothing read back by the host.
-void join_launch(const JoinArgs& a, hipStream_t s);
-// The host checks of the join arrays (hgx_join.hip): HGX_E_INVALID naming the join query and the part.
-void join_validate(int32_t n_queries, const int64_t* part_off, const int32_t* part_pos, int32_t flags);
+// Enqueues the join on s: no synchronisation, nothing read back by the host.  k0 / k1 (both or neither): events
+// recorded around the keep kernel.
+void join_launch(const JoinArgs& a, hipStream_t s, hipEvent_t k0 = nullptr, hipEvent_t k1 = nullptr);
+// The host checks of the join arrays (hgx_join.hip): HGX_E_INVALID naming the join query and the part.  who: the
+// entry point's name; known_flags: the flag bits it takes.
+void join_validate(int32_t n_queries, const int64_t* part_off, const int32_t* part_pos, int32_t flags,
+                   const char* who = "hgx_pattern_batch_join", int32_t known_flags = HGX_JOIN_TYPE_SCAN);
+// The host checks of hgx_pattern_batch_atoms's keep table (hgx_atoms.hip): every predicate belongs to g's
+// snapshot, else HGX_E_INVALID naming the join query.  Returns the queries that carry one.
+int64_t atoms_keep_validate(const hgx_graph* g, int32_t n_queries, hgx_atom_predicate* const* keep);
+// HGX_E_UNSUPPORTED (who names the entry point) unless g's snapshot has an atom-type column; takes the snapshot's
+// mutex, so the caller holds none.
+void atoms_require_types(hgx_graph* g, const char* who);
 
 // The negation program of a DNF batch (hgx_pattern_batch_dnf_not, include/hgx_not.h) as the caller handed
 // it over; not_validate fills the totals.
@@ -796,8 +829,13 @@ struct ScanArgs {
     unsigned long long* out_ctr;    // [8] mapped: ctr
 };
 size_t scan_temp_bytes(int64_t n_chunks, hipStream_t s);
-// Enqueues the scan stage on s: no synchronisation, nothing read back by the host.
-void scan_launch(const ScanArgs& a, hipStream_t s);
+// Enqueues the scan stage on s: no synchronisation, nothing read back by the host.  atoms: a.idx is the atom index
+// (hgx_atoms.hip), whose node records take the node rules of include/hgx_atoms.h.
+void scan_launch(const ScanArgs& a, hipStream_t s, bool atoms = false);
+// The atom index of g's snapshot, built on first use (hgx_atoms.hip; caller holds g->mu, g's device current; a
+// context takes its snapshot's under the snapshot's mutex).  HGX_E_UNSUPPORTED (who names the entry point): no
+// atom-type column.
+std::shared_ptr<AtomIndex> ensure_atom_index(hgx_graph* g, const char* who);
 }  // namespace hgx
 
 // One batch (<= 1024 seeds) of a batched BFS and the result object of hgx_bfs_batch (hgx_bfs.hip makes and

@@ -19,7 +19,9 @@
 //        field, so part s still owns [uoff[s], uoff[s+1]) of the sorted keys, now ascending by value;
 //   hgx_join_keep  -- a lane per sorted key.  The driver of join query j is its part with the fewest hits
 //        (ties: the lowest index).  A key is kept iff it belongs to its query's driver, is no sentinel, differs
-//        from its predecessor and a binary search finds its value in the segment of every other part of j;
+//        from its predecessor and a binary search finds its value in the segment of every other part of j.  With
+//        atom predicates (hgx_pattern_batch_atoms, include/hgx_atoms.h) the FILTER instantiation tests the value's
+//        bit in its query's bitmap after the driver test and before those searches;
 //   the scan       -- pre = exclusive prefix sum of the keep flags (rocPRIM);
 //   hgx_join_place -- a kept key's value goes to pre[i]; qoff[j] = pre[uoff[part_off[j]]]; lane 0 publishes
 //        the totals and the counters into the mapped result area.
@@ -90,11 +92,15 @@ __global__ void __launch_bounds__(256) hgx_join_key(JoinArgs a) {
     wave_add(a.ctr + 5, targets_read);
 }
 
+// FILTER (hgx_pattern_batch_atoms with predicates): a key that is the first of its value in its query's driver
+// part tests its bit in the query's bitmap (one 8-byte load) before the probes of the other parts.  A batch
+// without predicates runs the instantiation without the test.
+template <bool FILTER>
 __global__ void __launch_bounds__(256) hgx_join_keep(JoinArgs a) {
     if (a.stat[2]) return;
     const int64_t H = a.uoff[a.n_parts];
     const u64* __restrict__ ks = a.key_sorted;
-    u64 probes = 0, distinct = 0;
+    u64 probes = 0, distinct = 0, tested = 0, rejected = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < H; i += (int64_t)gridDim.x * blockDim.x) {
         const u64 k = ks[i];
         const int64_t s = (int64_t)(k >> 32);
@@ -115,6 +121,14 @@ __global__ void __launch_bounds__(256) hgx_join_keep(JoinArgs a) {
                 }
             }
             keep = s == drv;
+            if (FILTER && keep) {
+                const u64* __restrict__ bits = a.keep_bits[j];
+                if (bits) {   // (v is an atom of the snapshot: a link atom or a target, below the bitmap's end)
+                    ++tested;
+                    keep = (bits[v >> 6] >> (v & 63)) & 1ull;
+                    if (!keep) ++rejected;
+                }
+            }
             for (int64_t t = s0; t < s1 && keep; ++t) {
                 if (t == s) continue;
                 const int64_t tb = a.uoff[t], te = a.uoff[t + 1];
@@ -127,10 +141,14 @@ __global__ void __launch_bounds__(256) hgx_join_keep(JoinArgs a) {
     }
     wave_add(a.ctr + 1, distinct);
     wave_add(a.ctr + 4, probes);
+    if (FILTER) {
+        wave_add(a.ctr + 6, tested);
+        wave_add(a.ctr + 7, rejected);
+    }
 }
 
 // out_ctr: [0] hits projected, [1] distinct values of the parts, [2] ids kept, [3] probes of the key kernel,
-// [4] probes of the keep kernel, [5] targets read.
+// [4] probes of the keep kernel, [5] targets read, [6] values tested by the filter, [7] values it rejected.
 __global__ void __launch_bounds__(256) hgx_join_place(JoinArgs a) {
     if (a.stat[2]) return;
     const int64_t H = a.uoff[a.n_parts];
@@ -143,10 +161,11 @@ __global__ void __launch_bounds__(256) hgx_join_place(JoinArgs a) {
 
 }  // namespace
 
-void join_validate(int32_t n_queries, const int64_t* part_off, const int32_t* part_pos, int32_t flags) {
-    const std::string who = "hgx_pattern_batch_join: ";
+void join_validate(int32_t n_queries, const int64_t* part_off, const int32_t* part_pos, int32_t flags, const char* name,
+                   int32_t known_flags) {
+    const std::string who = std::string(name) + ": ";
     if (n_queries < 0 || !part_off) fail(HGX_E_INVALID, who + "bad argument");
-    if (flags & ~HGX_JOIN_TYPE_SCAN) fail(HGX_E_INVALID, who + "unknown flag");
+    if (flags & ~known_flags) fail(HGX_E_INVALID, who + "unknown flag");
     if (part_off[0] != 0) fail(HGX_E_INVALID, who + "part_off[0] is not 0");
     for (int32_t j = 0; j < n_queries; ++j)
         if (part_off[j + 1] < part_off[j])
@@ -168,7 +187,7 @@ size_t join_temp_bytes(int64_t cap, int32_t sort_bits, hipStream_t s) {
     return sb;
 }
 
-void join_launch(const JoinArgs& a, hipStream_t s) {
+void join_launch(const JoinArgs& a, hipStream_t s, hipEvent_t k0, hipEvent_t k1) {
     const int grid = grid_for(a.cap, 256, 4096);
     HGX_HIP(hipMemsetAsync(a.ctr, 0, sizeof(u64) * 8, s));
     hgx_join_key<<<grid, 256, 0, s>>>(a);
@@ -176,8 +195,11 @@ void join_launch(const JoinArgs& a, hipStream_t s) {
     size_t sb = a.sort_tmp_bytes;
     HGX_HIP(rocprim::radix_sort_keys(a.sort_tmp, sb, (const u64*)a.key, a.key_sorted, (size_t)a.cap, 0u,
                                      (unsigned)a.sort_bits, s));
-    hgx_join_keep<<<grid, 256, 0, s>>>(a);
+    if (k0) HGX_HIP(hipEventRecord(k0, s));
+    if (a.keep_bits) hgx_join_keep<true><<<grid, 256, 0, s>>>(a);
+    else hgx_join_keep<false><<<grid, 256, 0, s>>>(a);
     HGX_CHECK_LAUNCH();
+    if (k1) HGX_HIP(hipEventRecord(k1, s));
     sb = a.tmp_bytes;
     HGX_HIP(rocprim::exclusive_scan(a.tmp, sb, (const uint8_t*)a.keep, a.pre, (int64_t)0, (size_t)a.cap + 1,
                                     rocprim::plus<int64_t>(), s));

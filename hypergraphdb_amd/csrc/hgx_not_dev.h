@@ -102,8 +102,21 @@ __device__ __forceinline__ bool leaf_satisfies(int32_t kind, const int32_t* __re
     }
 }
 
+// The satisfies of one leaf on a NODE atom of the type `type` (include/hgx_atoms.h): arity(k) holds iff k == 0
+// (ArityCondition.java:54-55), a type leaf compares the atom's type, every leaf that reads targets is false --
+// an empty orderedLink() / link() included, which holds on a link without targets.
+__device__ __forceinline__ bool node_leaf_satisfies(int32_t kind, const int32_t* __restrict__ op, int32_t m, int32_t type) {
+    if (kind == HGX_NOT_TYPE) {
+        for (int32_t i = 0; i < m; ++i)
+            if (op[i] == type) return true;
+        return false;
+    }
+    return kind == HGX_NOT_ARITY && op[0] == 0;
+}
+
 // The negations [g0, g1) of one clause on the link L: true iff no negated tree holds (a negated tree holds
-// when one of its terms has every literal holding).
+// when one of its terms has every literal holding).  NODE: the atom is a node of the type `type` (L is not read).
+template <bool NODE = false>
 __device__ __forceinline__ bool negations_keep(const NotDev& prog, int64_t g0, int64_t g1, const Link& L,
                                                const int32_t* __restrict__ link_type, int64_t row, int32_t& type,
                                                u64& types_read) {
@@ -114,7 +127,9 @@ __device__ __forceinline__ bool negations_keep(const NotDev& prog, int64_t g0, i
             bool all = true;
             for (int64_t l = prog.lit_off[t], l1 = prog.lit_off[t + 1]; l < l1 && all; ++l) {
                 const int4 rec = prog.lit[l];
-                const bool s = leaf_satisfies(rec.x, prog.ops + rec.z, rec.w - rec.z, L, link_type, row, type, types_read);
+                const bool s = NODE ? node_leaf_satisfies(rec.x, prog.ops + rec.z, rec.w - rec.z, type)
+                                    : leaf_satisfies(rec.x, prog.ops + rec.z, rec.w - rec.z, L, link_type, row, type,
+                                                     types_read);
                 all = s == (rec.y != 0);
             }
             p = all;

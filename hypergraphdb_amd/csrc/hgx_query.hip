@@ -1079,6 +1079,10 @@ struct hgx_query_result {
     // algorithmic bytes of the join stage
     int64_t join_parts = 0, hits_projected = 0, values_distinct = 0, join_kept = 0;
     double ms_join = 0, bytes_join = 0;
+    // hgx_pattern_batch_atoms: join queries with a predicate, values its bits tested / rejected, device ms of the
+    // keep kernel that holds the filter and the filter's algorithmic bytes
+    int64_t queries_filtered = 0, values_tested = 0, values_rejected = 0;
+    double ms_filter = 0, bytes_filter = 0;
 };
 
 // A packed batch resident in device memory (hgx_query_set_create), in the staging layout of the
@@ -1149,6 +1153,13 @@ struct JoinPlan {
     int32_t n_queries = 0;
     const int64_t* part_off = nullptr;   // [n_queries + 1]
     const int32_t* part_pos = nullptr;   // [part_off[n_queries]]
+    // hgx_pattern_batch_atoms (include/hgx_atoms.h): the bits of each join query's predicate (device pointers,
+    // null entries: none; null: no predicate in the batch), the queries that carry one, and whether the scanned
+    // clauses read the atom index instead of the link index
+    const u64* const* keep_bits = nullptr;   // [n_queries]
+    int64_t n_filtered = 0;
+    bool atom_scan = false;
+    const char* who = "hgx_pattern_batch_join";
 };
 
 template <class Get>
@@ -1429,6 +1440,8 @@ struct Front {
     const JoinPlan* join = nullptr;
     const int64_t* join_part_off = nullptr;   //   device copies
     const int32_t* join_part_pos = nullptr;
+    const u64* const* join_keep = nullptr;    //   (hgx_pattern_batch_atoms with predicates)
+    std::shared_ptr<AtomIndex> atom_index;    //   the index its scanned clauses read (else the link index)
 };
 
 // Buffers taken from the graph pool for one call, released on every exit path.
@@ -1452,6 +1465,7 @@ struct Events {
     hipEvent_t nt = nullptr;  // start of the negation filter (DNF batches with negations only)
     hipEvent_t sn = nullptr;  // start of the scan stage (DNF batches with scanned clauses only)
     hipEvent_t jn = nullptr;  // start of the join stage (join batches only)
+    hipEvent_t k0 = nullptr, k1 = nullptr;   // around the join's keep kernel (batches with atom predicates only)
     bool on = false;
     void init(hgx_graph* gg) {
         g = gg;
@@ -1469,6 +1483,11 @@ struct Events {
     void rec(int i, hipStream_t s) { if (on) HGX_HIP(hipEventRecord(e[i], s)); }
     void rec_extra(hipEvent_t& x, hipStream_t s) {
         if (!on) return;
+        take_extra(x);
+        HGX_HIP(hipEventRecord(x, s));
+    }
+    void take_extra(hipEvent_t& x) {   // (recorded by the stage's launcher)
+        if (!on) return;
         if (!x) {
             if (!g->ev_pool.empty()) {
                 x = g->ev_pool.back();
@@ -1477,7 +1496,6 @@ struct Events {
                 HGX_HIP(hipEventCreate(&x));
             }
         }
-        HGX_HIP(hipEventRecord(x, s));
     }
     void rec_union(hipStream_t s) { rec_extra(u, s); }
     void rec_not(hipStream_t s) { rec_extra(nt, s); }
@@ -1490,6 +1508,8 @@ struct Events {
         if (nt) g->ev_pool.push_back(nt);
         if (sn) g->ev_pool.push_back(sn);
         if (jn) g->ev_pool.push_back(jn);
+        if (k0) g->ev_pool.push_back(k0);
+        if (k1) g->ev_pool.push_back(k1);
     }
 };
 
@@ -1530,6 +1550,8 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     const JoinPlan* jp = f.join;
     const size_t o_jo = jp ? u.take(sizeof(int64_t) * ((size_t)jp->n_queries + 1)) : 0,
                  o_jp = jp ? u.take(sizeof(int32_t) * (size_t)f.n_or) : 0;
+    const bool jk = jp && jp->keep_bits && jp->n_queries > 0;
+    const size_t o_jk = jk ? u.take(sizeof(u64*) * (size_t)jp->n_queries) : 0;
     char* h = (char*)g->pinned_buf(u.off);
     auto put = [&](size_t o, const auto& v) {
         if (!v.empty()) std::memcpy(h + o, v.data(), sizeof(v[0]) * v.size());
@@ -1550,6 +1572,7 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     if (jp) {
         std::memcpy(h + o_jo, jp->part_off, sizeof(int64_t) * ((size_t)jp->n_queries + 1));
         if (f.n_or > 0) std::memcpy(h + o_jp, jp->part_pos, sizeof(int32_t) * (size_t)f.n_or);
+        if (jk) std::memcpy(h + o_jk, jp->keep_bits, sizeof(u64*) * (size_t)jp->n_queries);
     }
     if (np) {
         const int64_t zero = 0;   // (a program without terms has no lit_off)
@@ -1587,6 +1610,7 @@ void front_host(hgx_graph* g, int32_t n, const NormBatch& nb, Scratch& sc, Event
     if (jp) {
         f.join_part_off = (const int64_t*)(d + o_jo);
         f.join_part_pos = (const int32_t*)(d + o_jp);
+        if (jk) f.join_keep = (const u64* const*)(d + o_jk);
     }
     f.cond_bytes = 20.0 * nb.anchors.size() + 4.0 * nb.types.size() + 4.0 * nb.pos.size() +
                    4.0 * nb.pattern.size() + (double)sizeof(QDesc) * n;
@@ -1798,7 +1822,7 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             sa.desc = f.scan_desc;
             sa.chunk_beg = f.scan_chunk_beg;
             sa.clause_chunk = f.scan_clause_chunk;
-            sa.idx = g->type_idx;
+            sa.idx = f.atom_index ? f.atom_index->idx : g->type_idx;
             sa.tgt_idx = g->tgt_idx;
             sa.word = (u64*)w.take(sizeof(u64) * (size_t)sp.n_chunks);
             sa.cnt = (int64_t*)w.take(sizeof(int64_t) * ((size_t)sp.n_chunks + 1));
@@ -1848,6 +1872,11 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
             un.out_ids = (int32_t*)w.take(sizeof(int32_t) * (size_t)capK);
             ja.uoff = un.out_off;
             ja.uids = un.out_ids;
+            ja.keep_bits = f.join_keep;
+            if (ja.keep_bits) {
+                ev.take_extra(ev.k0);
+                ev.take_extra(ev.k1);
+            }
         }
         const int64_t nbp = std::max<int64_t>(1, ceil_div(capC, kPlaceChunks));
         // derived flat index: no scan launch between the front kernel and the match (its counter shards
@@ -1911,7 +1940,7 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         }
         if (scan) {
             ev.rec_scan(s);
-            scan_launch(sa, s);
+            scan_launch(sa, s, f.atom_index != nullptr);
         }
         if (dnf) {
             ev.rec_union(s);
@@ -1919,7 +1948,7 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
         }
         if (jp) {
             ev.rec_join(s);
-            join_launch(ja, s);
+            join_launch(ja, s, ev.k0, ev.k1);
         }
         ev.rec(3, s);
         if (flag) {
@@ -1988,6 +2017,19 @@ void back_end_sp(hgx_graph* g, int32_t n, Front& f, Scratch& sc, Events& ev, hgx
                 float c = 0;
                 HGX_HIP(hipEventElapsedTime(&c, ev.jn, ev.e[3]));
                 r->ms_join = c;
+            }
+            if (ja.keep_bits) {
+                // algorithmic bytes of the filter: per value tested the query's bitmap pointer
+                // and the word that holds the bit (16 B)
+                r->queries_filtered = jp->n_filtered;
+                r->values_tested = (int64_t)jc[6];
+                r->values_rejected = (int64_t)jc[7];
+                r->bytes_filter = 16.0 * (double)jc[6];
+                if (ev.on) {
+                    float c = 0;
+                    HGX_HIP(hipEventElapsedTime(&c, ev.k0, ev.k1));
+                    r->ms_filter = c;
+                }
             }
         }
         int64_t scan_kept = 0;
@@ -2107,8 +2149,11 @@ int run_batch(hgx_graph* g, int32_t n, NormBatch& nb, hgx_query_result** out) {
 // mutex itself, like run_batch_with (no cross-thread coalescing).
 // The scanned clauses of nb as the scan stage's plan: their segments from the type histogram (built on first
 // use; caller holds g->mu), cut into 64-entry chunks.
-void plan_scan(hgx_graph* g, int32_t n, const NormBatch& nb, const NotProgram* neg, ScanPlan& sp) {
-    ensure_type_index(g);
+void plan_scan(hgx_graph* g, int32_t n, const NormBatch& nb, const NotProgram* neg, ScanPlan& sp,
+               const AtomIndex* ai = nullptr) {
+    if (!ai) ensure_type_index(g);
+    const std::vector<int32_t>& type_key = ai ? ai->key : g->type_key;
+    const std::vector<int64_t>& type_seg = ai ? ai->seg : g->type_seg;
     sp.clauses = (int32_t)nb.scan.size();
     sp.clause_chunk.assign((size_t)n + 1, 0);
     sp.chunk_beg.assign(1, 0);
@@ -2124,12 +2169,12 @@ void plan_scan(hgx_graph* g, int32_t n, const NormBatch& nb, const NotProgram* n
         }
         const NormBatch::ScanClause& sc = nb.scan[k++];
         if (sc.nop) continue;
-        const auto it = std::lower_bound(g->type_key.begin(), g->type_key.end(), sc.type);
-        if (it == g->type_key.end() || *it != sc.type) continue;
-        const size_t ti = (size_t)(it - g->type_key.begin());
+        const auto it = std::lower_bound(type_key.begin(), type_key.end(), sc.type);
+        if (it == type_key.end() || *it != sc.type) continue;
+        const size_t ti = (size_t)(it - type_key.begin());
         ScanDesc d{};
-        d.seg_beg = g->type_seg[ti];
-        d.seg_len = g->type_seg[ti + 1] - d.seg_beg;
+        d.seg_beg = type_seg[ti];
+        d.seg_len = type_seg[ti + 1] - d.seg_beg;
         d.g0 = g0;
         d.g1 = g1;
         d.clause = c;
@@ -2159,6 +2204,7 @@ int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t
     r->n = join ? join->n_queries : n_or;   // (a join batch: the Or queries are the parts of the join queries)
     r->offsets.assign((size_t)r->n + 1, 0);
     if (join) r->join_parts = n_or;
+    if (join && join->keep_bits) r->queries_filtered = join->n_filtered;
     if (n > 0) {
         std::lock_guard<std::mutex> lk(g->mu);
         HGX_HIP(hipSetDevice(g->device));
@@ -2174,7 +2220,8 @@ int run_batch_dnf(hgx_graph* g, int32_t n_or, const int64_t* clause_off, int32_t
         f.join = join;
         ScanPlan sp;
         if (!nb.scan.empty()) {   // (hgx_pattern_batch_dnf_scan only; none: exactly hgx_pattern_batch_dnf_not)
-            plan_scan(g, n, nb, neg, sp);
+            if (join && join->atom_scan) f.atom_index = ensure_atom_index(g, join->who);
+            plan_scan(g, n, nb, neg, sp, f.atom_index.get());
             f.scan = &sp;
         }
         front_host(g, n, nb, sc, ev, f);
@@ -2498,21 +2545,36 @@ int hgx_pattern_batch_dnf_scan(hgx_graph* g, int32_t n_queries, const int64_t* c
 
 // hgx_pattern_batch_join (include/hgx_join.h): the parts are the queries of a DNF batch with a join plan.  An
 // error of the DNF entry names the part as its "query"; the message is put behind the join query and the part.
-int hgx_pattern_batch_join(hgx_graph* g, int32_t n_queries, const int64_t* part_off, const int32_t* part_pos,
-                           const int64_t* clause_off, const int64_t* type_off, const int32_t* types,
-                           const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off, const int32_t* pos,
-                           const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat, const int32_t* arity,
-                           const int64_t* neg_off, const int64_t* term_off, const int64_t* lit_off, const int32_t* lit,
-                           const int32_t* ops, int64_t n_ops, int32_t flags, hgx_query_result** out) {
+// keep != nullptr or atoms: hgx_pattern_batch_atoms (include/hgx_atoms.h), whose flag scans the atom index.
+static int join_entry(const char* name, bool atoms, hgx_graph* g, int32_t n_queries, const int64_t* part_off,
+                      const int32_t* part_pos, hgx_atom_predicate* const* keep, const int64_t* clause_off,
+                      const int64_t* type_off, const int32_t* types, const int64_t* inc_off, const int32_t* inc,
+                      const int64_t* pos_off, const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off,
+                      const int32_t* pat, const int32_t* arity, const int64_t* neg_off, const int64_t* term_off,
+                      const int64_t* lit_off, const int32_t* lit, const int32_t* ops, int64_t n_ops, int32_t flags,
+                      hgx_query_result** out) {
     HGX_API_BEGIN
-    if (!g || !out) fail(HGX_E_INVALID, "hgx_pattern_batch_join: bad argument");
+    const std::string who = std::string(name) + ": ";
+    if (!g || !out) fail(HGX_E_INVALID, who + "bad argument");
     *out = nullptr;
-    join_validate(n_queries, part_off, part_pos, flags);
-    if (g->shard) fail(HGX_E_UNSUPPORTED, "hgx_pattern_batch_join: not available on a partition shard");
+    join_validate(n_queries, part_off, part_pos, flags, name, atoms ? HGX_ATOMS_TYPE_SCAN : HGX_JOIN_TYPE_SCAN);
+    if (g->shard) fail(HGX_E_UNSUPPORTED, who + "not available on a partition shard");
     JoinPlan jp;
     jp.n_queries = n_queries;
     jp.part_off = part_off;
     jp.part_pos = part_pos;
+    jp.who = name;
+    jp.atom_scan = atoms && (flags & HGX_ATOMS_TYPE_SCAN) != 0;
+    std::vector<const u64*> bits;
+    if (keep) {
+        jp.n_filtered = atoms_keep_validate(g, n_queries, keep);
+        if (jp.n_filtered > 0) {
+            bits.resize((size_t)n_queries);
+            for (int32_t j = 0; j < n_queries; ++j) bits[j] = keep[j] ? keep[j]->bits : nullptr;
+            jp.keep_bits = bits.data();
+        }
+    }
+    if (jp.atom_scan) atoms_require_types(g, name);
     NotProgram p;
     p.neg_off = neg_off;
     p.term_off = term_off;
@@ -2522,7 +2584,7 @@ int hgx_pattern_batch_join(hgx_graph* g, int32_t n_queries, const int64_t* part_
     p.n_ops = n_ops;
     const int32_t n_parts = (int32_t)part_off[n_queries];
     const int rc = dnf_entry(g, n_parts, clause_off, type_off, types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat,
-                             arity, neg_off ? &p : nullptr, out, (flags & HGX_JOIN_TYPE_SCAN) != 0, &jp);
+                             arity, neg_off ? &p : nullptr, out, flags != 0, &jp);
     if (rc != HGX_OK) {
         std::string msg = hgx_last_error(), at;
         const size_t k = msg.find("query ");
@@ -2533,8 +2595,43 @@ int hgx_pattern_batch_join(hgx_graph* g, int32_t n_queries, const int64_t* part_
                 at = "join query " + std::to_string(j) + " part " + std::to_string(s - part_off[j]) + ": ";
             }
         }
-        fail(rc, "hgx_pattern_batch_join: " + at + msg);
+        fail(rc, who + at + msg);
     }
+    HGX_API_END
+}
+
+int hgx_pattern_batch_join(hgx_graph* g, int32_t n_queries, const int64_t* part_off, const int32_t* part_pos,
+                           const int64_t* clause_off, const int64_t* type_off, const int32_t* types,
+                           const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off, const int32_t* pos,
+                           const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat, const int32_t* arity,
+                           const int64_t* neg_off, const int64_t* term_off, const int64_t* lit_off, const int32_t* lit,
+                           const int32_t* ops, int64_t n_ops, int32_t flags, hgx_query_result** out) {
+    return join_entry("hgx_pattern_batch_join", false, g, n_queries, part_off, part_pos, nullptr, clause_off, type_off,
+                      types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat, arity, neg_off, term_off, lit_off, lit,
+                      ops, n_ops, flags, out);
+}
+
+int hgx_pattern_batch_atoms(hgx_graph* g, int32_t n_queries, const int64_t* part_off, const int32_t* part_pos,
+                            hgx_atom_predicate* const* keep, const int64_t* clause_off, const int64_t* type_off,
+                            const int32_t* types, const int64_t* inc_off, const int32_t* inc, const int64_t* pos_off,
+                            const int32_t* pos, const int64_t* pset_off, const int64_t* pat_off, const int32_t* pat,
+                            const int32_t* arity, const int64_t* neg_off, const int64_t* term_off,
+                            const int64_t* lit_off, const int32_t* lit, const int32_t* ops, int64_t n_ops,
+                            int32_t flags, hgx_query_result** out) {
+    return join_entry("hgx_pattern_batch_atoms", true, g, n_queries, part_off, part_pos, keep, clause_off, type_off,
+                      types, inc_off, inc, pos_off, pos, pset_off, pat_off, pat, arity, neg_off, term_off, lit_off, lit,
+                      ops, n_ops, flags, out);
+}
+
+int hgx_query_result_atoms_stats(const hgx_query_result* r, int64_t* queries_filtered, int64_t* values_tested,
+                                 int64_t* values_rejected, double* ms_filter, double* bytes_filter) {
+    HGX_API_BEGIN
+    if (!r) fail(HGX_E_INVALID, "hgx_query_result_atoms_stats: null result");
+    if (queries_filtered) *queries_filtered = r->queries_filtered;
+    if (values_tested) *values_tested = r->values_tested;
+    if (values_rejected) *values_rejected = r->values_rejected;
+    if (ms_filter) *ms_filter = r->ms_filter;
+    if (bytes_filter) *bytes_filter = r->bytes_filter;
     HGX_API_END
 }
 

@@ -17,7 +17,8 @@
 //        negations on the row it holds (the walk and the leaves of hgx_not_dev.h; all 64 lanes belong to one
 //        clause, so the program reads are wave-uniform).  Targets are loaded only when a literal of the
 //        clause reads them; the clause's type is known from the segment, so link_type is never read.  One
-//        ballot gives the chunk's keep word and count;
+//        ballot gives the chunk's keep word and count.  Over the atom index (hgx_atoms.hip) the
+//        ATOMS instantiation walks a node record's negations by the node rules of include/hgx_atoms.h;
 //   the scan         -- cpre = exclusive prefix sum of the chunk counts (rocPRIM);
 //   hgx_scan_offsets -- the merged run offsets (the clause stage's + the scanned rows kept before each clause)
 //        and the workspace check: anchored + scanned hits beyond the capacity set the clause stage's overflow
@@ -79,6 +80,9 @@ __device__ __forceinline__ void wave_range(int64_t n_chunks, int64_t& c0, int64_
     c1 = c0 + per < n_chunks ? c0 + per : n_chunks;
 }
 
+// ATOMS: a.idx is the atom index (hgx_atoms.hip); a node record (high offset word kAtomNode, arity 0) walks its
+// negations by the node rules of include/hgx_atoms.h.  The link index runs the instantiation without the branch.
+template <bool ATOMS>
 __global__ void __launch_bounds__(256) hgx_scan_eval(ScanArgs a) {
     const int lane = threadIdx.x & 63;
     if (blockIdx.x == 0 && threadIdx.x == 0) a.cnt[a.n_chunks] = 0;
@@ -104,7 +108,14 @@ __global__ void __launch_bounds__(256) hgx_scan_eval(ScanArgs a) {
             }
             if (keep) {
                 keep = (d.arity < 0 || cur.y == d.arity) && cur.y >= d.min_arity;
-                if (keep && d.g0 < d.g1) {
+                if (ATOMS && keep && d.g0 < d.g1 && cur.w == kAtomNode) {
+                    ++walked;
+                    Link L;
+                    L.n = 0;
+                    L.tg = nullptr;
+                    int32_t type = d.type;
+                    keep = negations_keep<true>(a.prog, d.g0, d.g1, L, nullptr, 0, type, types_read);
+                } else if (keep && d.g0 < d.g1) {
                     ++walked;
                     Link L;
                     L.n = cur.y;
@@ -266,10 +277,11 @@ size_t scan_temp_bytes(int64_t n_chunks, hipStream_t s) {
     return sb;
 }
 
-void scan_launch(const ScanArgs& a, hipStream_t s) {
+void scan_launch(const ScanArgs& a, hipStream_t s, bool atoms) {
     HGX_HIP(hipMemsetAsync(a.ctr, 0, sizeof(u64) * 8, s));
     const int wgrid = grid_for(a.n_chunks * 64, 256, 4096);
-    hgx_scan_eval<<<wgrid, 256, 0, s>>>(a);
+    if (atoms) hgx_scan_eval<true><<<wgrid, 256, 0, s>>>(a);
+    else hgx_scan_eval<false><<<wgrid, 256, 0, s>>>(a);
     HGX_CHECK_LAUNCH();
     size_t sb = a.tmp_bytes;
     HGX_HIP(rocprim::exclusive_scan(a.tmp, sb, (const int64_t*)a.cnt, a.cpre, (int64_t)0, (size_t)a.n_chunks + 1,

@@ -258,6 +258,7 @@ int hgx_graph_set_atom_types(hgx_graph* g, const int32_t* atom_type) {
     }
     if (g->atom_type) (void)hipFree(g->atom_type);   // (every evaluation that read it has been waited for)
     g->atom_type = fresh;
+    g->atom_index.reset();   // (include/hgx_atoms.h: the next scan over the atoms builds it from the new column)
     HGX_API_END
 }
 

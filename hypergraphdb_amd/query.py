@@ -30,6 +30,12 @@ Reference (C = core/src/java/org/hypergraphdb):
     device call through hgx_pattern_batch_join (include/hgx_join.h) -- the sorted SET of the projected atoms (the
     reference delivers duplicates in the inner order), a link too short for i contributing nothing (the
     reference's getTargetAt throws ArrayIndexOutOfBoundsException there).
+  * Over every atom (include/hgx_atoms.h): with the atom types set (snapshot.set_atom_types) a clause without an
+    anchor scans the ATOM index -- nodes and links of the type, the reference's indexByType.find(T) -- and a
+    type tree next to projections, and(type(Person), apply(targetAt(g, 1), ...)), restricts the projected atoms
+    through an AtomPredicate.  Here: atom_parts + pattern_batch_atoms; find_all routes the two shapes it
+    otherwise refuses there when, and only when, the snapshot has atom types.  A node atom takes the
+    reference's satisfies rules (node_satisfies).
 """
 from __future__ import annotations
 
@@ -39,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HGXUnsupported, check, lib, ptr
-from .algorithms import AtomTypeCondition, DefaultALGenerator, HGException, bfs_sequence
+from .algorithms import AtomPredicate, AtomTypeCondition, DefaultALGenerator, HGException, bfs_sequence
 
 ANY = _lib.HGX_ANY_HANDLE
 
@@ -565,8 +571,11 @@ def decode_negations(neg_off, term_off, lit_off, lit, ops):
 
 
 class QueryResult:
-    def __init__(self, offsets, ids, ms=None, union=None, negation=None, scan=None, join=None):
+    def __init__(self, offsets, ids, ms=None, union=None, negation=None, scan=None, join=None, atoms=None):
         self.offsets, self.ids, self.ms = offsets, ids, ms
+        # pattern_batch_atoms: {"queries_filtered", "values_tested", "values_rejected", "ms_filter", "bytes_filter"}
+        # (hgx_query_result_atoms_stats; all zero on any other result)
+        self.atoms = atoms
         # pattern_batch_join: {"parts", "hits_projected", "values_distinct", "kept", "ms_join", "bytes_join"}
         # (hgx_query_result_join_stats; all zero on a pattern_batch_dnf result)
         self.join = join
@@ -726,7 +735,10 @@ def pattern_batch_dnf_arrays(snapshot, clause_off, type_off, types, inc_off, inc
     return _read_dnf_result(h, n)
 
 
-def _read_dnf_result(h, n, scan=False) -> QueryResult:
+def _read_dnf_result(h, n, scan=False, atoms=False) -> QueryResult:
+    qf, vt, vr, ms_f, by_f = C.c_int64(), C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+    rc5 = lib().hgx_query_result_atoms_stats(h, C.byref(qf), C.byref(vt), C.byref(vr), C.byref(ms_f),
+                                             C.byref(by_f)) if atoms else _lib.HGX_OK
     ch, kept, ms_u, by_u = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
     rc = lib().hgx_query_result_union_stats(h, C.byref(ch), C.byref(kept), C.byref(ms_u), C.byref(by_u))
     te, rj, ms_n, by_n = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
@@ -742,6 +754,10 @@ def _read_dnf_result(h, n, scan=False) -> QueryResult:
     check(rc2)
     check(rc3)
     check(rc4)
+    check(rc5)
+    if atoms:
+        r.atoms = {"queries_filtered": qf.value, "values_tested": vt.value, "values_rejected": vr.value,
+                   "ms_filter": ms_f.value, "bytes_filter": by_f.value}
     r.join = {"parts": pa.value, "hits_projected": hp.value, "values_distinct": vd.value, "kept": jk.value,
               "ms_join": ms_j.value, "bytes_join": by_j.value}
     if scan:
@@ -934,6 +950,135 @@ def pattern_batch_join(snapshot, queries, type_scan=False) -> QueryResult:
                                      *(encode_negations(negs) if any(negs) else (None,) * 5), type_scan=type_scan)
 
 
+# --- the pattern path over every atom: atom-index scans and a predicate on projected atoms (include/hgx_atoms.h) ---
+
+def node_satisfies(leaf, type_) -> bool:
+    """The leaf's own satisfies() on a NODE atom of this type key (include/hgx_atoms.h): arity(k) holds iff
+    k == 0 (ArityCondition.java:54-55); every leaf that reads targets is false, an empty orderedLink() / link()
+    included (OrderedLinkCondition.java:100-101, LinkCondition.java:119-120, PositionedIncidentCondition.java:
+    134-135, IncidentCondition.java:71-75) -- raw_satisfies makes those two true on a link without targets, so a
+    node is not an arity-0 link."""
+    if isinstance(leaf, (AtomTypeCondition, TypePlusCondition)):
+        return raw_satisfies(leaf, (), type_)
+    if isinstance(leaf, ArityCondition):
+        return leaf.arity == 0
+    if isinstance(leaf, (IncidentCondition, PositionedIncidentCondition, OrderedLinkCondition, LinkCondition)):
+        return False
+    raise TypeError(leaf)
+
+
+def is_type_tree(c) -> bool:
+    """``c`` is an And / Or / Not tree over hg.type / hg.typePlus alone: what an AtomPredicate evaluates."""
+    if isinstance(c, (And, Or)):
+        return len(c) > 0 and all(is_type_tree(x) for x in c)
+    if isinstance(c, Not):
+        return is_type_tree(c.negated)
+    return isinstance(c, (AtomTypeCondition, TypePlusCondition))
+
+
+def atom_parts(cond, snapshot=None):
+    """``cond`` -> (parts, tree) of one query of pattern_batch_atoms: the parts [(pos, condition)] as join_parts
+    makes them, and the type tree that becomes the query's predicate (None: no predicate).  As join_parts, with
+    one addition: when the And has at least one projection, its sub-conditions that are pure type trees (And /
+    Or / Not over hg.type / hg.typePlus) form the predicate instead of a scanned plain part.  A condition
+    without any projection is one plain part (a DNF query over the atoms) and has no predicate."""
+    subs = [cond] if isinstance(cond, MapCondition) else _flatten(cond, []) if isinstance(cond, And) else None
+    if subs is None or not any(isinstance(c, MapCondition) for c in subs):
+        _check_part(cond, cond)
+        return [(None, cond)], None
+    trees = [c for c in subs if not isinstance(c, MapCondition) and is_type_tree(c)]
+    others = [c for c in subs if isinstance(c, MapCondition) or not is_type_tree(c)]
+    parts = join_parts(others[0] if len(others) == 1 else And(others), snapshot)
+    return parts, (None if not trees else trees[0] if len(trees) == 1 else And(trees))
+
+
+def pattern_batch_atoms_arrays(snapshot, part_off, part_pos, keep, clause_off, type_off, types, inc_off, inc, pos_off,
+                               pos, pset_off, pat_off, pat, arity, neg_off=None, term_off=None, lit_off=None, lit=None,
+                               ops=None, type_scan=True) -> QueryResult:
+    """Flat batch for hgx_pattern_batch_atoms (include/hgx_atoms.h): the arrays of pattern_batch_join_arrays, and
+    ``keep``: None, or one AtomPredicate or None per join query -- the query's result is restricted to the atoms
+    the predicate keeps.  ``type_scan``: clauses without an anchor scan the ATOM index (nodes and links of the
+    type).  ``result.atoms`` holds the filter's statistics."""
+    part_off = np.ascontiguousarray(part_off, np.int64)
+    part_pos = np.ascontiguousarray(part_pos, np.int32)
+    clause_off = np.ascontiguousarray(clause_off, np.int64)
+    n = len(part_off) - 1
+    keep_arr = None
+    if keep is not None:
+        if len(keep) != n:
+            raise ValueError("keep must have one entry per query")
+        keep_arr = (C.c_void_p * max(n, 1))(*[None if k is None else k.handle for k in keep])
+    if neg_off is None:
+        neg_off = term_off = lit_off = np.zeros(0, np.int64)
+        lit = ops = np.zeros(0, np.int32)
+    arrs = [np.ascontiguousarray(type_off, np.int64), np.ascontiguousarray(types, np.int32),
+            np.ascontiguousarray(inc_off, np.int64), np.ascontiguousarray(inc, np.int32),
+            np.ascontiguousarray(pos_off, np.int64), np.ascontiguousarray(pos, np.int32),
+            np.ascontiguousarray(pset_off, np.int64), np.ascontiguousarray(pat_off, np.int64),
+            np.ascontiguousarray(pat, np.int32), np.ascontiguousarray(arity, np.int32),
+            np.ascontiguousarray(neg_off, np.int64), np.ascontiguousarray(term_off, np.int64),
+            np.ascontiguousarray(lit_off, np.int64), np.ascontiguousarray(lit, np.int32),
+            np.ascontiguousarray(ops, np.int32)]
+    h = C.c_void_p()
+    check(lib().hgx_pattern_batch_atoms(snapshot.handle, n, part_off.ctypes.data,
+                                        part_pos.ctypes.data if part_pos.size else None,
+                                        None if keep_arr is None else C.cast(keep_arr, C.c_void_p),
+                                        clause_off.ctypes.data, *(a.ctypes.data if a.size else None for a in arrs),
+                                        len(arrs[-1]), _lib.HGX_ATOMS_TYPE_SCAN if type_scan else 0, C.byref(h)))
+    return _read_dnf_result(h, n, scan=True, atoms=True)
+
+
+def pattern_batch_atoms(snapshot, queries, keep=None, type_scan=True) -> QueryResult:
+    """pattern_batch_join over every atom, in one device call (include/hgx_atoms.h).  Every query is a list of
+    (pos, cond) parts or a condition atom_parts lowers -- its type trees next to projections become the query's
+    predicate.  ``keep``: None, or per query an AtomPredicate, a raw tree over hg.type / hg.typePlus, or None;
+    the query's result is restricted to the atoms it keeps (together with the tree atom_parts found, if any).  A
+    raw tree is compiled once per distinct tree per call against the snapshot's atom types and released on
+    return.  ``type_scan`` (on by default here): a clause without an incidence anchor is split into one clause
+    per type and scanned over the atom index -- every atom of the type that passes, NODE atoms included, by the
+    node rules of node_satisfies; it needs the atom types (HGXUnsupported without them).  A query without parts
+    is empty.  ``result.atoms``: {"queries_filtered", "values_tested", "values_rejected", "ms_filter",
+    "bytes_filter"}; ``result.join`` / ``union`` / ``negation`` / ``scan`` as for pattern_batch_join
+    (values_distinct before the filter, kept after it; rows_scanned counts atom-index rows)."""
+    queries = list(queries)
+    if keep is not None and len(keep) != len(queries):
+        raise ValueError("keep must have one entry per query")
+    part_off, part_pos, clause_off, norm, negs, preds = [0], [], [0], [], [], []
+    for j, q in enumerate(queries):
+        parts, tree = (q, None) if type(q) in (list, tuple) else atom_parts(q, snapshot)
+        k = None if keep is None else keep[j]
+        if tree is not None and k is not None:
+            if isinstance(k, AtomPredicate):
+                raise ValueError(f"query {j}: an AtomPredicate next to the type tree {tree!r} (pass a raw tree)")
+            k = And([tree, k])
+        preds.append(tree if k is None else k)
+        for pos, cond in parts:
+            if pos is not None and pos < 0:
+                raise ValueError(f"bad target position {pos}")
+            part_pos.append(JOIN_SELF if pos is None else int(pos))
+            _lower_dnf_query(cond, type_scan, norm, negs)
+            clause_off.append(len(norm))
+        part_off.append(len(part_pos))
+    compiled = {}
+    try:
+        handles = None
+        if any(p is not None for p in preds):
+            handles = []
+            for p in preds:
+                if p is not None and not isinstance(p, AtomPredicate):
+                    key = _tree_key(p)
+                    if key not in compiled:
+                        compiled[key] = AtomPredicate(snapshot, p)
+                    p = compiled[key]
+                handles.append(p)
+        return pattern_batch_atoms_arrays(snapshot, part_off, part_pos, handles, clause_off, *_ext_arrays(norm),
+                                          *(encode_negations(negs) if any(negs) else (None,) * 5),
+                                          type_scan=type_scan)
+    finally:
+        for p in compiled.values():
+            p.close()
+
+
 def pattern_batch_dnf(snapshot, queries, type_scan=False) -> QueryResult:
     """Evaluate many And / Or trees over the accelerated leaves in one device call: every query goes
     through to_dnf, its clauses run as one hgx_pattern_batch_ext-shaped batch and are united on the device
@@ -1112,7 +1257,23 @@ def _find_all_join(snapshot, cond):
 
 
 def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
-    """hg.findAll(graph, cond) for the accelerated shapes."""
+    """hg.findAll(graph, cond) for the accelerated shapes.  On a snapshot with atom types
+    (``snapshot.set_atom_types``), and only there, two shapes every other route refuses go through
+    pattern_batch_atoms: a condition whose DNF has a typed clause without an incidence anchor (the scan then
+    delivers the nodes of the type too), and an And of type trees with projections."""
+    try:
+        return _find_all(snapshot, cond, config)
+    except HGXUnsupported:
+        if getattr(snapshot, "atom_type", None) is None or isinstance(cond, BFSCondition):
+            raise
+        try:
+            return list(pattern_batch_atoms(snapshot, [cond])[0].tolist())
+        except HGXUnsupported:
+            pass
+        raise
+
+
+def _find_all(snapshot, cond, config):
     if isinstance(cond, BFSCondition):
         # TraversalBasedQuery(traversal, ReturnType.targets) (ToQueryMap.java:313-319): the atoms
         # in HGBreadthFirstTraversal.next() order
@@ -1125,7 +1286,7 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
             return compiler.getQuery(snapshot, cond).execute()
         except HGXUnsupported:
             pass   # a mapping or an inner condition the join does not take: the host path below
-        return sorted({v for v in (cond.mapping(x) for x in find_all(snapshot, cond.cond, config)) if v is not None})
+        return sorted({v for v in (cond.mapping(x) for x in _find_all(snapshot, cond.cond, config)) if v is not None})
     if isinstance(cond, Or) or (isinstance(cond, And) and _has_or(cond)) or _has_not(cond):
         compiler = (config.compiler(Or) if config else None) or GpuOrToQuery()
         try:
@@ -1135,16 +1296,16 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
                 raise   # a Not over anything but the accelerated leaves, or without an anchor: the CPU's query
             # a part the pattern engine does not take (Map / BFS sub-conditions): host set algebra
         if isinstance(cond, Or):
-            return sorted(set().union(*(find_all(snapshot, c, config) for c in cond)))
+            return sorted(set().union(*(_find_all(snapshot, c, config) for c in cond)))
         joined = _find_all_join(snapshot, cond)
         if joined is not None:
             return joined
         subs = _flatten(cond, [])
         own = (MapCondition, BFSCondition, Or)
-        sets = [set(find_all(snapshot, c, config)) for c in subs if isinstance(c, own)]
+        sets = [set(_find_all(snapshot, c, config)) for c in subs if isinstance(c, own)]
         rest = [c for c in subs if not isinstance(c, own)]
         if rest:
-            sets.append(set(find_all(snapshot, And(rest), config)))
+            sets.append(set(_find_all(snapshot, And(rest), config)))
         return sorted(set.intersection(*sets))
     if isinstance(cond, And):
         subs = _flatten(cond, [])
@@ -1154,10 +1315,10 @@ def find_all(snapshot, cond, config: HGQueryConfiguration | None = None):
             joined = _find_all_join(snapshot, cond)
             if joined is not None:
                 return joined
-            sets = [set(find_all(snapshot, c, config)) for c in subs if isinstance(c, (MapCondition, BFSCondition))]
+            sets = [set(_find_all(snapshot, c, config)) for c in subs if isinstance(c, (MapCondition, BFSCondition))]
             rest = [c for c in subs if not isinstance(c, (MapCondition, BFSCondition))]
             if rest:
-                sets.append(set(find_all(snapshot, And(rest), config)))
+                sets.append(set(_find_all(snapshot, And(rest), config)))
             return sorted(set.intersection(*sets))
     compiler = (config.compiler(And) if config else None) or GpuAndToQuery()
     return compiler.getQuery(snapshot, cond).execute()

@@ -157,6 +157,11 @@ class HyperGraphSnapshot:
         self.num_incidences = i.value
         self._row_of = None
         self._keep_host = keep_host
+        # the host mirror of the atom-type column in a holder shared with the contexts (an update drops the column)
+        if getattr(self, "_atom_type", None) is None:
+            self._atom_type = [None]
+        else:
+            self._atom_type[0] = None
         if not keep_host:
             # large benchmark graphs: the device copy is authoritative
             self.tgt_idx = None
@@ -270,6 +275,20 @@ class HyperGraphSnapshot:
         check(lib().hgx_graph_type_links(self.handle, ptr(t), len(t), ptr(out)))
         return out
 
+    def type_atoms(self, types) -> np.ndarray:
+        """The number of atoms, nodes and links, of each type key (hgx_graph_type_atoms, include/hgx_atoms.h): the
+        size of the type's segment of the device atom index, built on first use from the atom types
+        (``set_atom_types``; HGXUnsupported without them).  0 for an absent key."""
+        t = np.ascontiguousarray(np.atleast_1d(types), np.int32)
+        out = np.zeros(len(t), np.int64)
+        check(lib().hgx_graph_type_atoms(self.handle, ptr(t), len(t), ptr(out)))
+        return out
+
+    @property
+    def atom_type(self):
+        """The host mirror of the atom types (``set_atom_types``), or None: a context sees its snapshot's."""
+        return self._atom_type[0]
+
     def set_atom_types(self, atom_type):
         """The type key of every atom, link atoms and node atoms alike (hgx_graph_set_atom_types,
         include/hgx_sibling.h): what a type tree used as a sibling predicate is evaluated against.  One value
@@ -277,11 +296,13 @@ class HyperGraphSnapshot:
         again afterwards.  Not on a context."""
         if atom_type is None:
             check(lib().hgx_graph_set_atom_types(self.handle, None))
+            self._atom_type[0] = None
             return
         t = np.ascontiguousarray(atom_type, np.int32)
         if t.shape != (self.A,):
             raise ValueError("atom_type must have one entry per atom")
         check(lib().hgx_graph_set_atom_types(self.handle, ptr(t)))
+        self._atom_type[0] = t.copy()
 
     def context(self):
         """An execution context of this snapshot (hgx_graph_context): shares the device arrays, has its
@@ -294,6 +315,7 @@ class HyperGraphSnapshot:
         ctx._attach(h, self.device, self.A, self.link_atom, self.tgt_off, self.tgt_idx, self.link_type,
                     self._keep_host)
         ctx._row_of = self._row_of
+        ctx._atom_type = self._atom_type
         return ctx
 
     def set_timing(self, on=True):

@@ -15,8 +15,8 @@
  *   hgx_bfs_batch_sib, hgx_shortest_paths_sib
  *                              <- the traversals of hgx.h / hgx_paths.h with such a generator.
  *
- * Not accelerated with a sibling predicate: the order-exact sequence (hgx_bfs_sequence*), partition shards, the
- * JNI shim, and node atoms in type scans (hgx_scan.h).
+ * Not accelerated with a sibling predicate: the order-exact sequence (hgx_bfs_sequence*), partition shards and the
+ * JNI shim.  (Node atoms in type scans read the atom-type column of this header through hgx_atoms.h.)
  */
 #ifndef HGX_SIBLING_H
 #define HGX_SIBLING_H
