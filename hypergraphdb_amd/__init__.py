@@ -6,7 +6,9 @@ This package is the host-side mirror of the reference interfaces on that path:
   algorithms                    DefaultALGenerator / HGBreadthFirstTraversal / bfs_batch; LinkPredicate: any tree of
                                 hg.and_ / or_ / not_ over the accelerated leaves as a generator's link predicate
                                 (include/hgx_linkpred.h); AtomPredicate: a type tree or a per-atom mask as its
-                                sibling predicate (include/hgx_sibling.h)
+                                sibling predicate (include/hgx_sibling.h); BfsResult.sets / reachable_batch ->
+                                VisitedSets: the visited sets of many seeds, optionally filtered by an atom
+                                predicate, as one CSR built on the device (include/hgx_sets.h)
   query                         hg.and/or/type/incident/orderedLink, GpuAndToQuery, GpuOrToQuery, pattern_batch,
                                 pattern_batch_dnf (include/hgx_dnf.h); hg.not_ on its clauses (include/hgx_not.h);
                                 opt-in type-index scans of clauses without an anchor: pattern_batch_dnf(...,
@@ -22,8 +24,8 @@ This package is the host-side mirror of the reference interfaces on that path:
 """
 from ._lib import HGXError, HGXUnsupported, lib  # noqa: F401
 from .algorithms import (AtomPredicate, AtomTypeCondition, BfsResult, DefaultALGenerator, HGBreadthFirstTraversal,  # noqa: F401
-                         HopPaths, LinkPredicate, SequenceResult, bfs_sequence,
-                         HGException, bfs_batch)
+                         HopPaths, LinkPredicate, SequenceResult, VisitedSets, bfs_sequence,
+                         HGException, bfs_batch, reachable_batch)
 from .classics import GraphClassics, LinkWeights, ShortestPathsResult, hop_paths, shortest_paths  # noqa: F401
 from .query import (And, ArityCondition, GpuAndToQuery, GpuMapToQuery, GpuOrToQuery, GpuScanToQuery,  # noqa: F401
                     HGQueryConfiguration, LinkCondition, MapCondition, Not, Or, PositionedIncidentCondition, TargetAt,

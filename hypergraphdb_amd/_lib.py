@@ -123,6 +123,14 @@ EXPORTED_HOPS = (
     "hgx_hop_paths_free", "hgx_bfs_result_depth_row", "hgx_bfs_result_predecessor_row",
 )
 
+# Every symbol include/hgx_sets.h declares (checked by tests/test_sets_abi.py without a GPU).
+EXPORTED_SETS = (
+    "hgx_bfs_result_sets", "hgx_visited_sets_info", "hgx_visited_sets_offsets", "hgx_visited_sets_read",
+    "hgx_visited_sets_stats", "hgx_visited_sets_free",
+)
+HGX_SETS_DEPTHS = 1
+HGX_SETS_COUNT_ONLY = 2
+
 
 class GraphDesc(C.Structure):
     _fields_ = [("num_atoms", C.c_int64), ("num_links", C.c_int64), ("link_atom", C.c_void_p),
@@ -344,6 +352,14 @@ def lib():
         "hgx_atom_predicate_flags": ([vp, i64, i64, vp], C.c_int),
         "hgx_bfs_batch_sib": ([vp, vp, i32, i32, C.POINTER(AlgenOpts), vp, vp, C.POINTER(vp)], C.c_int),
         "hgx_shortest_paths_sib": ([vp, vp, vp, i32, C.POINTER(AlgenOpts), vp, vp, vp, C.POINTER(vp)], C.c_int),
+        # include/hgx_sets.h
+        "hgx_bfs_result_sets": ([vp, vp, i32, i32, i32, vp, C.c_uint32, i64, C.POINTER(vp)], C.c_int),
+        "hgx_visited_sets_info": ([vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(C.c_uint32)], C.c_int),
+        "hgx_visited_sets_offsets": ([vp, vp], C.c_int),
+        "hgx_visited_sets_read": ([vp, i64, i64, vp, vp], C.c_int),
+        "hgx_visited_sets_stats": ([vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double)], C.c_int),
+        "hgx_visited_sets_free": ([vp], None),
     }
     for name, (args, res) in sig.items():
         if LIB_VARIANT and not hasattr(L, name):

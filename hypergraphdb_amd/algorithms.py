@@ -359,6 +359,37 @@ class BfsResult:
         check(lib().hgx_bfs_result_predecessor_row(self.handle, int(seed_index), int(first), int(n), ptr(pa), ptr(pl)))
         return pa[:n], pl[:n]
 
+    def sets(self, seed_indices=None, min_depth=0, max_depth=None, where=None, depths=False, count_only=False,
+             max_entries=None) -> "VisitedSets":
+        """The visited sets of many seeds in one device pass (hgx_sets.h): set i = the ascending atoms the
+        traversal of seed ``seed_indices[i]`` (None: every seed) reached at a depth in [min_depth, max_depth]
+        (None: to the last level; min_depth 0 includes the seed), and that satisfy ``where`` -- an AtomPredicate,
+        a tree over hg.type / hg.typePlus (compiled for this call), or one truth value per atom.  ``where``
+        filters what is reported, not what the traversal expanded.  ``depths``: keep each entry's depth;
+        ``count_only``: the offsets alone; ``max_entries``: refuse (HGX_E_NOMEM) a larger result."""
+        si = np.arange(self.n_seeds, dtype=np.int32) if seed_indices is None else \
+            np.ascontiguousarray(seed_indices, np.int32)
+        if si.ndim != 1:
+            raise ValueError("seed_indices: a 1-d sequence")
+        owned = None
+        if where is None or isinstance(where, AtomPredicate):
+            ap = where
+        elif isinstance(where, (np.ndarray, list, tuple)):
+            ap = owned = AtomPredicate.from_mask(self.snapshot, where)
+        else:
+            ap = owned = AtomPredicate(self.snapshot, where)
+        flags = (_lib.HGX_SETS_DEPTHS if depths else 0) | (_lib.HGX_SETS_COUNT_ONLY if count_only else 0)
+        md = _lib.HGX_UNBOUNDED if max_depth is None or max_depth >= 2**31 - 1 else int(max_depth)
+        h = C.c_void_p()
+        try:
+            check(lib().hgx_bfs_result_sets(self.handle, ptr(si), len(si), int(min_depth), md,
+                                            None if ap is None else ap.handle, flags,
+                                            -1 if max_entries is None else int(max_entries), C.byref(h)))
+        finally:
+            if owned is not None:
+                owned.close()   # the call held its own reference
+        return VisitedSets(h, self.seeds[si] if len(si) else np.zeros(0, np.int32), owner=self)
+
     def stats(self, accounting=True, raw=False):
         """Kernel timings (timing enabled), algorithmic bytes; with ``accounting`` also the
         TEPS numerator, |U_d| and the SURVEY.md 8(d) bytes (runs the accounting kernels).
@@ -467,6 +498,103 @@ def bfs_batch(snapshot, seeds, max_depth=None, generator: DefaultALGenerator | N
         for p in owned:
             p.close()   # the result holds its own references
     return BfsResult(snapshot, h, s)
+
+
+class VisitedSets:
+    """The visited sets of a selection of seeds as one CSR (hgx_visited_sets; device resident until read).
+    ``offsets`` [n + 1], ``counts`` [n], ``total``; ``self[i]``: set i's ascending atoms, or (atoms, depths) when
+    made with depths; ``flat()``: the flat arrays.  A count-only object has offsets and counts alone."""
+
+    def __init__(self, handle, starts, owner=None):
+        self._h = handle
+        self.starts = starts
+        self.owner = owner          # the BfsResult the sets were read from
+        self.owns_result = False    # reachable_batch: the BfsResult was made for this object and closes with it
+        n, tot, fl = C.c_int32(), C.c_int64(), C.c_uint32()
+        check(lib().hgx_visited_sets_info(handle, C.byref(n), C.byref(tot), C.byref(fl)))
+        self.n_sets, self.total = n.value, tot.value
+        self.with_depths = bool(fl.value & _lib.HGX_SETS_DEPTHS)
+        self.count_only = bool(fl.value & _lib.HGX_SETS_COUNT_ONLY)
+        self.offsets = np.zeros(self.n_sets + 1, np.int64)
+        check(lib().hgx_visited_sets_offsets(handle, ptr(self.offsets)))
+        self.counts = np.diff(self.offsets)
+        self._atoms = self._depths = None
+
+    @property
+    def handle(self):
+        if self._h is None:
+            raise ValueError("result closed")
+        return self._h
+
+    def read(self, first: int = 0, n: int | None = None):
+        """The entries [first, first + n) of the flat arrays (cut at the end): atoms, or (atoms, depths)."""
+        n = self.total - first if n is None else n
+        k = max(min(n, self.total - first), 0)
+        atoms = np.empty(max(k, 1), np.int32)
+        deps = np.empty(max(k, 1), np.int32) if self.with_depths else None
+        check(lib().hgx_visited_sets_read(self.handle, int(first), int(n), ptr(atoms),
+                                          None if deps is None else ptr(deps)))
+        return (atoms[:k], deps[:k]) if self.with_depths else atoms[:k]
+
+    def flat(self):
+        """The flat arrays, read once: atoms, or (atoms, depths)."""
+        if self._atoms is None:
+            got = self.read()
+            self._atoms, self._depths = got if self.with_depths else (got, None)
+        return (self._atoms, self._depths) if self.with_depths else self._atoms
+
+    def __len__(self):
+        return self.n_sets
+
+    def __getitem__(self, i: int):
+        if not -self.n_sets <= i < self.n_sets:
+            raise IndexError(i)
+        self.flat()
+        i %= self.n_sets
+        o, e = int(self.offsets[i]), int(self.offsets[i + 1])
+        return (self._atoms[o:e], self._depths[o:e]) if self.with_depths else self._atoms[o:e]
+
+    def stats(self) -> dict:
+        rr, ts = C.c_int64(), C.c_int64()
+        ms, by = C.c_double(), C.c_double()
+        check(lib().hgx_visited_sets_stats(self.handle, C.byref(rr), C.byref(ts), C.byref(ms), C.byref(by)))
+        return {"rows_read": rr.value, "tiles_skipped": ts.value, "ms_total": ms.value, "bytes": by.value}
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            lib().hgx_visited_sets_free(self._h)
+            self._h = None
+            if self.owns_result and self.owner is not None:
+                self.owner.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def reachable_batch(snapshot, starts, generator: DefaultALGenerator | None = None, max_depth=None, where=None,
+                    include_start=False, **kw) -> VisitedSets:
+    """For every start: ``find_all(snapshot, hg.and_(where, hg.bfs(start, ...)))`` as a sorted set -- the atoms a
+    breadth-first traversal of ``generator`` reaches from it within ``max_depth`` that satisfy ``where`` -- for
+    many starts at once: ``bfs_batch`` followed by ``BfsResult.sets`` in one call.  ``include_start``: the start
+    itself is a member (subject to ``where``); a traversal never returns it.  ``kw``: depths, count_only,
+    max_entries of ``BfsResult.sets``.  The traversal's result closes with the returned object."""
+    res = bfs_batch(snapshot, starts, max_depth, generator)
+    try:
+        vs = res.sets(None, 0 if include_start else 1, None, where, **kw)
+    except BaseException:
+        res.close()
+        raise
+    vs.owns_result = True
+    return vs
 
 
 class SequenceResult:

@@ -33,6 +33,7 @@
 #include "../../include/hgx_not.h"
 #include "../../include/hgx_paths.h"
 #include "../../include/hgx_scan.h"
+#include "../../include/hgx_sets.h"
 #include "../../include/hgx_sibling.h"
 
 namespace hgx {
@@ -525,6 +526,10 @@ void bfs_batch_sib(hgx_graph* g, const int32_t* seeds, int32_t n_seeds, int32_t 
 void shortest_paths_sib(hgx_graph* g, const int32_t* starts, const int32_t* goals, int32_t n_pairs,
                         const hgx_algen_opts* opts, const hgx_link_weights* w, hgx_link_predicate* p,
                         hgx_atom_predicate* ap, hgx_sp_result** out);
+// The argument checks of hgx_bfs_result_sets (include/hgx_sets.h; hgx_sets.hip), all decided on the host: the
+// statuses of the header's table, the messages naming the set.  n_result_seeds / shard: of the result asked.
+void sets_validate(bool have_result, bool have_out, bool shard, int32_t n_result_seeds, const int32_t* seed_index,
+                   int32_t n_sets, int32_t min_depth, int32_t max_depth, uint32_t flags);
 void graph_release(hgx_graph* g);
 void free_yield_lists(hgx_graph* g);   // (hgx_graph_update: the incidence changed)   // drop a reference; frees at zero
 // Builds the BFS's first-use read-only tables (has-incidence bitmap, yield flags, push chunks) on g
